@@ -17,7 +17,11 @@ Configs (BASELINE.json): default = configs[1]/[4] shape (B = 256 pairs in flight
 --n-az 4000 = configs[4] (256k-point scans); --mask-before-features --batch 32 = configs[2]
 (the features, and so the registration, see only the GMM background points).
 
-Inputs are resident in HBM before the timed region.  After the timed region a short kernel pass
+Inputs are resident in HBM before the timed region: every frame of a run while they fit
+--resident-gb (96 GB: 130 frames of the default shape), else a longer run walks the resident
+frames back and forth (reflect()), any --steps in the same memory.  A plain run sets up, warms up, times the
+steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.  With --full the
+CPU baseline legs run first, and after the timed region a short kernel pass
 re-runs a few steps on ONE stream with per-kernel HIP events (ssf_profile_enable), so the
 roofline fractions come from kernel-only durations (the timed run overlaps streams, where an
 event pair also counts time spent queued behind other streams' work-groups).
@@ -85,6 +89,53 @@ def _lib_sha16():
         return None
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 20240607
+
+
+def _sample(n, cap, seed):
+    """every index of range(n) when n <= cap, else cap seeded draws from it, ascending (the same
+    for the same n, cap and seed: two builds sample the same elements)"""
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=cap, dtype=np.int64))
+
+
+def step_outputs(pipe, res):
+    """{name: float32 / float64 array} of what the last timed step handed its caller (Pipeline.step's
+    result `res` and the pipeline's pose state), for --dump-outputs.  Per-point arrays are
+    sampled on the device (_sample); rows of the per-frame plane buffers that the step did not
+    write (past the frame's count, or without a plane fit) are given as 0."""
+    import torch
+    dev, B, N = pipe.dev, pipe.B, pipe.N
+    idx = lambda a: torch.from_numpy(a).to(dev)
+    pb, table = res["pb"], pipe.last_table
+    d = {"mask_pose": res["out"][:, :25].cpu().numpy(),      # every field up to LOWER_BOUND (ssf/_abi.py POSE_OUT)
+         "pose_rel": pipe.pose_rel.cpu().numpy(), "pose_abs": pipe.pose_abs.cpu().numpy(),
+         "plane_count": pb.count.to(torch.float64).cpu().numpy()}
+    d["bg_mask"] = res["bg"][idx(_sample(B * N, 2_000_000, DUMP_SEED))].to(torch.float32).cpu().numpy()
+    # plane points and their table: positions j of every frame's block, the same j for all frames
+    j = idx(_sample(pb.max_points, max(1, 1_250_000 // B), DUMP_SEED + 1))
+    rows = (pb.off[:B, None] + j[None, :]).reshape(-1)
+    live = (j[None, :] < pb.count[:, None]).reshape(-1)
+    fit = live & (table[1][rows] != 0)
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    d["plane_xyzi"] = torch.where(live[:, None], pb.xyzi[rows], zero).view(B, -1, 4).cpu().numpy()
+    d["plane_normal_valid"] = fit.view(B, -1).to(torch.float32).cpu().numpy()
+    d["plane_normal"] = torch.where(fit[:, None], table[0][rows], zero).view(B, -1, 3).cpu().numpy()
+    return d
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64, DUMP_MAX_BYTES in all"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES or any(a.dtype not in (np.float32, np.float64) for a in arrays.values()):
+        raise RuntimeError(f"--dump-outputs: {total} bytes / dtypes {sorted({str(a.dtype) for a in arrays.values()})}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -114,13 +165,28 @@ def parse(argv=None):
                     help="the mask reads float64 pos / flow (ssf_mask_pose_batch_f64: the reference's "
                          "dtype when its npz arrays are float64); the features keep the float32 cloud "
                          "(PointCloud2 carries f32).  72 B resident per point and step: use <= 30 steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="the default pipeline's extra measurements around the timed steps: the CPU "
+                         "baseline legs before them (cpu_baseline), the one-stream kernel pass after "
+                         "them (kernels, roofline*, north_star_*).  Without it the line holds the "
+                         "timed steps' figures only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its "
+                         "caller as DIR/<name>.npy (float32 / float64, at most 64 MB in all; large "
+                         "arrays as a fixed seeded sample).  Same arguments, same inputs: two "
+                         "builds can be compared output for output")
+    ap.add_argument("--resident-gb", type=float, default=96.0,
+                    help="HBM for the input frames of the default pipeline.  A run of more steps "
+                         "than frames fit walks the resident frames back and forth (106 frames of "
+                         "the no-flag shape take 78 GB: runs up to 100 steps see every frame once)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
                     help="CPU baseline: seconds per leg (single thread, all cores, sklearn)")
     ap.add_argument("--cpu-cores", type=int, default=None,
                     help="processes of the all-cores leg (default: this job's CPU share)")
     ap.add_argument("--kernel-pass", type=int, default=3,
-                    help="steps re-run on one stream with per-kernel events after the timed run")
+                    help="with --full: steps re-run on one stream with per-kernel events after the "
+                         "timed run")
     ap.add_argument("--serial", action="store_true", help="one stream (per-kernel timing without overlap)")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N>1 rehearsal on a one-GPU box: every rank on cuda:0, gloo collectives "
@@ -329,6 +395,49 @@ def frame_window(args, B, n_frames):
             "timed_frames": [args.warmup, args.warmup + args.steps]}
 
 
+def resident_frames(args, n_frames):
+    """Frames of each sequence kept in HBM: all n_frames a run steps through while they fit
+    --resident-gb (24 B per point, 72 with --f64-inputs), else as many as fit (at least 3)."""
+    per_frame = args.batch * args.rows * args.n_az * (72 if args.f64_inputs else 24)
+    return max(3, min(n_frames, int(args.resident_gb * 1e9) // per_frame))
+
+
+def reflect(k, m):
+    """Frame of step k when m frames are resident: 0, 1, .. m - 1, m - 2, .. 1, 0, 1, ..  A run
+    longer than its resident frames walks them back and forth, so every step still pairs two
+    neighbouring frames of the sequence (a wrap to frame 0 would pair its two ends)."""
+    r = k % (2 * (m - 1))
+    return r if r < m else 2 * (m - 1) - r
+
+
+class Frames:
+    """make_data's resident batches, indexed by step through reflect()"""
+
+    def __init__(self, batches):
+        self.batches = batches
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __getitem__(self, k):
+        return self.batches[reflect(k, len(self.batches))]
+
+    def turns(self, k):
+        """the pair of step k runs against the direction of step k - 1's (the walk turned)"""
+        m = len(self.batches)
+        return k >= 2 and reflect(k, m) - reflect(k - 1, m) != reflect(k - 1, m) - reflect(k - 2, m)
+
+
+def invert_poses(pose):
+    """[P, 7] f64 poses (q xyzw, t) -> their inverses (q*, -R(q)^T t), in place, on the current
+    stream"""
+    import torch
+    u, w, t = -pose[:, 0:3], pose[:, 3:4], -pose[:, 4:7]
+    c = torch.cross(u, t, dim=1)
+    pose[:, 4:7] = t + 2.0 * (w * c + torch.cross(u, c, dim=1))
+    pose[:, 0:3] = u
+
+
 def make_data(args, dev, n_frames, rank, batch=None):
     """[n_frames] batches of B frames: pos/flow packed [B*N, 3] f32, resident in HBM.  Sequence
     b of rank r is synth sequence r * 100000 + (b mod distinct), ray-cast on the GPU
@@ -382,6 +491,8 @@ class Pipeline:
             self.fe_reg.reserve(B, N)
         self.pose_rel = ssf.identity_poses(B, dev)
         self.pose_abs = ssf.identity_poses(B, dev)
+        with torch.cuda.stream(self.s_reg):     # load invert_poses' kernels now, not at a turn
+            invert_poses(ssf.identity_poses(B, dev))
         self.last = self.last_table = None
         self.last_e = self.last_etable = None
         # round 5: a ring of per-step output buffers (plane cloud, plane table, background mask),
@@ -512,6 +623,11 @@ class Pipeline:
             r0, r1 = mk(), mk()
             r0.record(s_reg)        # after the wait: registration time excludes queueing on s_feat
             if self.last is not None:
+                # a run longer than its resident frames walks them back and forth (Frames): where
+                # the walk turns, the warm start (the previous solution: the motion goes on as
+                # it was) is the previous solution's inverse
+                if streams is None and getattr(batches, "turns", None) and batches.turns(k):
+                    invert_poses(self.pose_rel)
                 edges = (self.last_e, self.last_etable, eb) if a.edges else None
                 res = self.fe_reg.register(self.last, self.last_table, pb, self.pose_rel, self.pose_abs,
                                            want_nlog=want_stats, edges=edges)
@@ -775,7 +891,7 @@ def latency(args):
     med = lambda v: float(np.median(v)) if len(v) else 0.0
     kernels = {name: dict(launches=n, ms=ms / n) for name, (n, ms) in sorted(kt.items(), key=lambda x: -x[1][1])}
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         iters_s = ["--rows", str(args.rows), "--n-az", str(args.n_az), "--solver", args.solver, "--iters", str(iters)]
         single = _run_legs([("oracle", 0, iters_s)], args.cpu_seconds)[0]
         if single.get("seconds"):
@@ -1158,6 +1274,9 @@ def main():
     args = parse()
     if args.hw_queues > 0:                # before anything starts the HIP runtime
         os.environ["GPU_MAX_HW_QUEUES"] = str(args.hw_queues)
+    if args.dump_outputs and (args.latency or args.consecutive or args.sequences_total):
+        sys.exit("bench.py --dump-outputs writes the default pipeline's step outputs; it is not "
+                 "available with --latency / --consecutive / --sequences-total")
     if args.latency:
         if args.gpus != 1 or os.environ.get("WORLD_SIZE", "1") != "1":
             sys.exit("bench.py --latency is a one-GPU, one-frame-pair measurement")
@@ -1202,7 +1321,7 @@ def main():
     if args.warmup < 1:
         args.warmup = 1  # the first frame of a sequence has no last frame to register against
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)          # before anything touches the GPU
 
     import torch
@@ -1218,7 +1337,7 @@ def main():
     B, N = args.batch, args.rows * args.n_az
     n_frames = args.warmup + args.steps + 1
     t_data = time.perf_counter()
-    batches = make_data(args, dev, n_frames, rank)
+    batches = Frames(make_data(args, dev, resident_frames(args, n_frames), rank))
     t_data = time.perf_counter() - t_data
     off, h_off = ssf.frame_offsets([N] * B, dev)
     pipe = Pipeline(args, dev, B, N, iters, world)
@@ -1238,9 +1357,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     mem0 = torch.cuda.memory_stats(dev)
+    res = None
     t0 = time.perf_counter()
     for k in range(args.warmup, args.warmup + args.steps):
-        pipe.step(k, batches, off, h_off, True)
+        res = pipe.step(k, batches, off, h_off, True)
     if world > 1:
         pipe.exchange()
     torch.cuda.synchronize()
@@ -1253,6 +1373,9 @@ def main():
     allocator = _alloc_delta(mem0, torch.cuda.memory_stats(dev))
     if args.dump_poses and rank == 0:
         np.save(args.dump_poses, pipe.pose_abs.cpu().numpy())
+    if args.dump_outputs and rank == 0 and res is not None:   # before the kernel pass restarts the chain
+        dump_outputs(args.dump_outputs, step_outputs(pipe, res))
+    del res
     gather_ok = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if backend == "gloo" else dev)
@@ -1273,7 +1396,7 @@ def main():
     overlapped = {k: avg_ms(v) for k, v in pipe.ev.items()}
     ks = list(range(args.warmup, min(args.warmup + args.kernel_pass, n_frames)))
     kernels, passes = {}, 0.0
-    if args.kernel_pass > 0:
+    if args.full and args.kernel_pass > 0:
         cfg = pipe.fe_feat.cfg
         times, acc = kernel_pass(pipe, batches, off, h_off, ks, args.rows, cfg.row_start, cfg.row_end)
         kernels, passes = rooflines(times, acc, B, N, args.layout)
@@ -1305,12 +1428,13 @@ def main():
                    "world_size_initialised": (dist.get_world_size() if world > 1 else 1),
                    "backend": backend or "none",
                    "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "0")) or None,
-                   "frame_window": frame_window(args, B, n_frames),
+                   "frame_window": {**frame_window(args, B, n_frames), "resident_frames": len(batches)},
                    "mask_schedule": {"order": args.mask_order, "queue": args.mask_queue},
                    **({"rehearsal": "all ranks on one GPU, gloo"} if args.rehearse_one_gpu else {})},
         "roofline": None, "cpu_baseline": cpu,
         "kernels": kernels, "overlapped_event_ms": overlapped,
-        "mask_passes_per_frame": passes, "gather_check": gather_ok,
+        "mask_passes_per_frame": passes if args.full else None, "gather_check": gather_ok,
+        "full": bool(args.full),
         "allocator_timed_region": allocator,
         "data_gen_s": round(t_data, 2), "lib_sha16": None,
     }

@@ -3,10 +3,10 @@
 Collect the passes separately (FETCH_SIZE needs 3 TCC counters, WRITE_SIZE 2; one run cannot
 hold both), on a serial bench command (one stream, so every launch is that kernel alone):
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o f -- python bench.py --serial ...
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o w -- python bench.py --serial ...
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch/f_counter_collection.csv \
-        gpurun_out/pmc_write/w_counter_collection.csv --bench-log gpurun_out/pmc_fetch.log \
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d rocprof_out/pmc_fetch -o f -- python bench.py --full --no-cpu-baseline --serial ...
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d rocprof_out/pmc_write -o w -- python bench.py --full --no-cpu-baseline --serial ...
+    python tools/pmc_traffic.py rocprof_out/pmc_fetch/f_counter_collection.csv \
+        rocprof_out/pmc_write/w_counter_collection.csv --bench-log rocprof_out/pmc_fetch.log \
         --out profiles/r02_traffic.json
 
 Units and corrections (/opt/skills/guides/MI355X_MICROARCH.md, "HBM [CDNA4]"): FETCH_SIZE and
