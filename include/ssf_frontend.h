@@ -188,6 +188,33 @@ int32_t ssf_register_batch(ssf_ctx* ctx, void* stream, int32_t n_pairs,
                            double* d_log, int32_t* d_nlog, int32_t* d_ncorr, int32_t* d_nn,
                            const float* d_last_strip_xyzi, const int32_t* d_last_strip_head);
 
+/* The association launch ssf_register_batch(_edges) / ssf_register_chain make for n_pairs pairs
+ * bounded by max_plane_points, given the sorted buffers of ssf_plane_table_batch (replaces: none
+ * -- the launcher's own choice, exported so that a test can prove which path a launch took).
+ * Host arithmetic only: no context, no HIP call.  SSF_E_ARG on n_pairs < 1, a negative bound or
+ * a null out.
+ *   strip_path  1: the y-strip association (max_plane_points within the LDS sort limit, 16384);
+ *               0: another association kernel, the other fields are 0
+ *   group_mode  1: one query per 16-lane group over qsplit work-groups per pair (launches of
+ *               <= 16 pairs); 0: the lane mode, one query per lane
+ *   soa         1: the last frame staged as 14-B SoA arrays (bound > 6144), 0: as 16-B points
+ *   qsplit      work-groups per pair; lane mode: min(8, 256 / n_pairs, ceil(bound / 1024))
+ *   lds_cap     last-frame points the launch stages in LDS (<= 10752); a longer last frame
+ *               walks the sorted copy in global memory
+ *   compacted   1: lane mode with qsplit == 1 and planes only -- the association writes the
+ *               valid records compacted in rank order and the solve streams them in; 0: records
+ *               in query order, the solve compacts them itself */
+typedef struct {
+    int32_t strip_path;
+    int32_t group_mode;
+    int32_t soa;
+    int32_t qsplit;
+    int32_t lds_cap;
+    int32_t compacted;
+} ssf_launch_plan;
+int32_t ssf_register_plan(int32_t n_pairs, int64_t max_plane_points, int32_t with_edges,
+                          ssf_launch_plan* out);
+
 /* A sequence's consecutive pairs in one call (lidarOdometry_onlyPC's frame loop over a sequence:
  * every pair is warm-started from the previous pair's solution, src/lidarOdometry_onlyPC.cpp:164,
  * 251-252).  Frames 0..n_pairs of ONE plane batch (d_off / d_count: n_pairs + 2 / n_pairs + 1

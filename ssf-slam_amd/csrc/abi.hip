@@ -554,6 +554,19 @@ int32_t ssf_register_batch(ssf_ctx* c, void* stream, int32_t n_pairs, const floa
     return SSF_OK;
 }
 
+int32_t ssf_register_plan(int32_t n_pairs, int64_t max_plane_points, int32_t with_edges,
+                          ssf_launch_plan* out) {
+    if (!out || n_pairs < 1 || max_plane_points < 0) return SSF_E_ARG;
+    const ssf::RegisterPlan r = ssf::register_plan(n_pairs, max_plane_points, with_edges != 0);
+    out->strip_path = r.strips;
+    out->group_mode = r.coop || r.bigc;
+    out->soa = r.soa;
+    out->qsplit = r.qsplit;
+    out->lds_cap = r.lds_cap;
+    out->compacted = r.compacted;
+    return SSF_OK;
+}
+
 int32_t ssf_register_chain(ssf_ctx* c, void* stream, int32_t n_pairs, const float* d_xyzi,
                            const int64_t* d_off, const int32_t* d_count, const float* d_normal,
                            const uint8_t* d_valid, const float* d_sorted_xyzi,

@@ -2795,7 +2795,7 @@ SSF_DEV void evaluate(const CorrLds& C, int nv, const double q[4], const double 
 }
 
 // The first evaluation over records the association compacted ([0, nv) of rec, rank order, all
-// valid, nv <= kSolveLdsCap): evaluate<NW>()'s loop -- the same records per thread in the same
+// valid, 1 <= nv <= kSolveLdsCap -- the clamped loads need a record): evaluate<NW>()'s loop -- the same records per thread in the same
 // order and the same sums -- with each record read from global memory and stored to the LDS
 // arrays the later evaluations read (positions i + h T of thread t are read back by thread t
 // only: no barrier).  The loads of a step are in flight together; the first evaluation's
@@ -3186,11 +3186,13 @@ __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
         for (int k = 0; k < 4; ++k) q[k] = S.q[k];
         for (int k = 0; k < 3; ++k) t[k] = S.t[k];
 #endif
-        if (ncp >= 0 && in_lds && SSF_SOLVE_DIRECT == 1) {
+        // (nv == 0 -- an empty current frame, or no valid correspondence -- has no record to load:
+        // evaluate_load's clamped loads would read rec[-1]; evaluate() from LDS gives the zero sums)
+        if (ncp > 0 && in_lds && SSF_SOLVE_DIRECT == 1) {
             evaluate_load<NT / 64>(rec, C, nv, q, t, ne, red, par);
             par ^= 1;
         } else {
-            if (ncp >= 0 && in_lds) {
+            if (ncp > 0 && in_lds && SSF_SOLVE_DIRECT != 1) {
                 // (A/B, SSF_SOLVE_DIRECT=2) a plain copy of the compacted records into LDS, four
                 // per thread in flight: thread t writes the positions t + k T it reads itself
                 const int T = blockDim.x;
@@ -3554,6 +3556,36 @@ hipError_t launch_plane_table(hipStream_t s, const ssf_config& cfg, int n_frames
     return hipGetLastError();
 }
 
+// The choice launch_register makes for a launch's association on the kSortMax strip path (host
+// only, no HIP call; ssf_register_plan exports it so that tests can prove which path a launch
+// took).  Few pairs (a node's one pair, configs[2]'s chained pairs) take the group mode: up to 8
+// work-groups per pair, each staging the last frame and taking a share of the queries, so the
+// launch spreads over ~256 CUs instead of n_pairs (every work-group stages the whole last frame,
+// so the split is capped at ~4 launch-filling waves of work-groups; the query loop strides over
+// gridDim.y).  Big launches: the lane mode (or SSF_ASSOC_BIG_G-lane groups, A/B), split over
+// min(8, 256 / n_pairs, ceil(max_m / kStripThreads)) work-groups per pair; with ONE work-group
+// per pair and planes only, the association hands the solve compacted records.
+RegisterPlan register_plan(int n_pairs, int64_t max_m, bool with_edges) {
+    RegisterPlan r{};
+#ifndef SSF_ASSOC_XBAND
+    if (n_pairs <= 0 || max_m <= 0 || max_m > kSortMax) return r;
+    r.strips = true;
+    r.soa = max_m > kAssocStripF4Max;
+    r.lds_cap = (int)std::min<int64_t>(max_m, r.soa ? kAssocStripSoaMax : kAssocStripF4Max);
+    r.coop = kAssocCoopG > 0 && n_pairs <= kAssocCoopPairs;
+    r.bigc = !r.coop && kAssocBigG > 0;
+    constexpr int kQpwCoop = kAssocCoopG > 0 ? kStripThreads / kAssocCoopG : kStripThreads;
+    r.qsplit = r.coop ? (int)std::min<int64_t>((max_m + kQpwCoop - 1) / kQpwCoop,
+                                               std::max(8, 1024 / n_pairs))
+                      : (int)std::max<int64_t>(1, std::min<int64_t>({8, 256 / n_pairs,
+                                               (max_m + kStripThreads - 1) / kStripThreads}));
+    r.compacted = !r.coop && !r.bigc && r.qsplit == 1 && !with_edges && !SSF_ASSOC_DEFER && SSF_ASSOC_COMPACT;
+#else
+    (void)n_pairs; (void)max_m; (void)with_edges;
+#endif
+    return r;
+}
+
 hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, const float4* last,
                            const int64_t* last_off, const int32_t* last_count,
                            const float* last_normal, const uint8_t* last_valid,
@@ -3574,26 +3606,12 @@ hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, co
     int32_t* ncp = nullptr;
     if (max_m > 0) {
         const int bx = (int)((max_m + 255) / 256);
-#ifndef SSF_ASSOC_XBAND
-        if (max_m <= kSortMax && last_sorted && last_sidx) {
-            const bool soa = max_m > kAssocStripF4Max;
-            const int cap = (int)std::min<int64_t>(max_m, soa ? kAssocStripSoaMax : kAssocStripF4Max);
+        const RegisterPlan plan = register_plan(n_pairs, max_m, edge != nullptr);
+        if (plan.strips && last_sorted && last_sidx) {
+            const bool soa = plan.soa, coop = plan.coop, bigc = plan.bigc;
+            const int cap = plan.lds_cap, qsplit = plan.qsplit;
             const size_t lds = soa ? (size_t)cap * 14 + 16 : (size_t)cap * sizeof(float4);
-            // few pairs (a node's one pair, configs[2]'s chained pairs): up to 8 work-groups per
-            // pair, each staging the last frame and taking a share of the queries, so the launch
-            // spreads over ~256 CUs instead of n_pairs
-            const bool coop = kAssocCoopG > 0 && n_pairs <= kAssocCoopPairs;
-            constexpr int kQpwCoop = kAssocCoopG > 0 ? kStripThreads / kAssocCoopG : kStripThreads;
-            // big launches: one work-group per pair, the lane mode (or SSF_ASSOC_BIG_G-lane groups, A/B)
-            const bool bigc = !coop && kAssocBigG > 0;
-            // (group mode: every work-group stages the whole last frame, so the split is capped at
-            // ~4 launch-filling waves of work-groups; the query loop strides over gridDim.y)
-            const int qsplit = coop ? (int)std::min<int64_t>((max_m + kQpwCoop - 1) / kQpwCoop,
-                                                             std::max(8, 1024 / n_pairs))
-                                    : (int)std::max<int64_t>(1, std::min<int64_t>({8, 256 / n_pairs,
-                                                             (max_m + kStripThreads - 1) / kStripThreads}));
-            if (!coop && !bigc && qsplit == 1 && nnv && ncompact && !edge && !SSF_ASSOC_DEFER && SSF_ASSOC_COMPACT)
-                ncp = ncompact;
+            if (plan.compacted && nnv && ncompact) ncp = ncompact;
             kmark(s, coop ? "k_associate_strips_coop" : soa ? "k_associate_strips_soa" : "k_associate_strips");
             hipLaunchKernelGGL(coop ? (soa ? k_associate_strips<true, kAssocCoopG> : k_associate_strips<false, kAssocCoopG>)
                                     : bigc ? (soa ? k_associate_strips<true, kAssocBigG> : k_associate_strips<false, kAssocBigG>)
@@ -3603,9 +3621,7 @@ hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, co
                                curr_count, pin, corr, nn, cap,
                                last_strip_head ? last_strip_xyzi : nullptr, last_strip_head,
                                ncp ? nnv : nullptr, ncp);
-        } else
-#endif
-        if (max_m <= kAssocSoaMax && last_sorted && last_sidx) {
+        } else if (max_m <= kAssocSoaMax && last_sorted && last_sidx) {
             const int qx = (int)((max_m + kAssocQ - 1) / kAssocQ);
             const bool soa = max_m > kAssocLdsMax;
             kmark(s, soa ? "k_associate_lds_soa" : "k_associate_lds");

@@ -135,6 +135,19 @@ hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, co
                            int32_t* ncompact = nullptr);
 // (nnv [>= the current frames' total points] and ncompact [>= n_pairs]: scratch that lets the
 // lane-mode association hand the solve compacted records; nullptr = records in query order)
+// What launch_register launches for the association of n_pairs pairs bounded by max_m plane
+// points, given the sorted buffers (and, for `compacted`, the nnv / ncompact scratch): host
+// arithmetic only.  strips = false: not the k_associate_strips path, the other fields are 0.
+struct RegisterPlan {
+    bool strips;      // k_associate_strips (max_m <= the LDS sort limit)
+    bool coop;        // group mode: one query per lane group, qsplit work-groups per pair
+    bool bigc;        // (A/B build only) lane groups for big launches too
+    bool soa;         // 14-B SoA staging instead of float4
+    bool compacted;   // the association writes compacted records and the solve streams them in
+    int qsplit;       // work-groups per pair
+    int lds_cap;      // last-frame points staged in LDS (a longer last frame walks global memory)
+};
+RegisterPlan register_plan(int n_pairs, int64_t max_m, bool with_edges);
 hipError_t launch_edge_table(hipStream_t s, const ssf_edge_config& ec, int n_frames,
                              const float4* edges, const int64_t* frame_off, const int32_t* count,
                              int64_t max_m, float* line, uint8_t* valid);

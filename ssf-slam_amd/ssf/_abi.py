@@ -39,7 +39,7 @@ EXPORTS = [
     "ssf_profile_read", "ssf_set_mask_split", "ssf_mask_pose_batch_f64",
     "ssf_edge_config_default", "ssf_set_edge_config", "ssf_extract_features_batch",
     "ssf_edge_table_batch", "ssf_register_batch_edges", "ssf_kabsch_f32_batch",
-    "ssf_set_mask_schedule",
+    "ssf_set_mask_schedule", "ssf_register_plan",
 ]
 # Every symbol include/ssf_pointnet2.h declares (TFlow point-set operators).
 PN2_EXPORTS = [
@@ -90,6 +90,12 @@ class EdgeConfig(C.Structure):
                 ("max_nn_d2", C.c_float)]
 
 
+class LaunchPlan(C.Structure):
+    """ssf_launch_plan: the association launch of a register call (ssf_register_plan)."""
+    _fields_ = [("strip_path", C.c_int32), ("group_mode", C.c_int32), ("soa", C.c_int32),
+                ("qsplit", C.c_int32), ("lds_cap", C.c_int32), ("compacted", C.c_int32)]
+
+
 _lib = None
 
 
@@ -135,6 +141,8 @@ def lib():
     L.ssf_register_chain.restype = i32
     L.ssf_register_pair.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, C.POINTER(StepLog)]
     L.ssf_register_pair.restype = i32
+    L.ssf_register_plan.argtypes = [i32, i64, i32, C.POINTER(LaunchPlan)]
+    L.ssf_register_plan.restype = i32
     L.ssf_set_mask_split.argtypes = [vp, i32]
     L.ssf_set_mask_split.restype = i32
     L.ssf_set_mask_schedule.argtypes = [vp, vp, i32, i32]

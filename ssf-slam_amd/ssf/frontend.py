@@ -42,6 +42,19 @@ def frame_offsets(counts, device):
     return h.to(device), h
 
 
+def register_plan(n_pairs: int, max_plane_points: int, with_edges: bool = False) -> dict:
+    """The association launch a register call of n_pairs pairs bounded by max_plane_points makes
+    (ssf_register_plan, host arithmetic only): dict(strip_path, group_mode, soa, compacted: bool;
+    qsplit, lds_cap: int)."""
+    plan = _abi.LaunchPlan()
+    rc = _abi.lib().ssf_register_plan(int(n_pairs), int(max_plane_points), 1 if with_edges else 0,
+                                      C.byref(plan))
+    if rc != _abi.SSF_OK:
+        raise ValueError(f"register_plan: bad arguments (n_pairs={n_pairs}, max_plane_points={max_plane_points})")
+    return dict(strip_path=bool(plan.strip_path), group_mode=bool(plan.group_mode), soa=bool(plan.soa),
+                qsplit=int(plan.qsplit), lds_cap=int(plan.lds_cap), compacted=bool(plan.compacted))
+
+
 @dataclass
 class PlaneBatch:
     """Plane clouds of F frames at frame offsets: xyzi[off[f] : off[f] + count[f]]."""

@@ -63,6 +63,60 @@ def test_error_paths_without_gpu():
     assert L.ssf_create(0, C.byref(cfg), C.byref(h)) == _abi.SSF_E_ARG
 
 
+def test_register_plan_table():
+    """ssf_register_plan against the launcher's documented rule (include/ssf_frontend.h, DESIGN
+    §6.4 / §6.5), written out here by hand: <= 16 pairs take the group mode; above, the lane mode
+    over qsplit = min(8, 256 / pairs, ceil(bound / 1024)) work-groups per pair; compacted records
+    iff lane mode, qsplit == 1 and planes only; float4 staging up to 6144 points, SoA above, at
+    most 10752 staged; the strip path up to 16384."""
+    import ssf
+    from ssf import _abi
+    for n in (1, 16):
+        for mx in (1, 64, 1024, 2369, 6145, 10753, 16384):
+            p = ssf.register_plan(n, mx)
+            assert p["strip_path"] and p["group_mode"] and not p["compacted"], (n, mx, p)
+            # group mode: 64 queries per work-group, capped at max(8, 1024 / pairs)
+            assert p["qsplit"] == min(-(-mx // 64), max(8, 1024 // n)), (n, mx, p)
+    lane = dict(strip_path=True, group_mode=False)
+    rows = [
+        (17, 2369, dict(lane, qsplit=3, compacted=False)),
+        (17, 1024, dict(lane, qsplit=1, compacted=True)),
+        (17, 1025, dict(lane, qsplit=2, compacted=False)),
+        (17, 986, dict(lane, qsplit=1, compacted=True)),
+        (18, 2369, dict(lane, qsplit=3, compacted=False)),
+        (20, 1601, dict(lane, qsplit=2, compacted=False)),
+        (32, 16384, dict(lane, qsplit=8, compacted=False)),
+        (128, 2369, dict(lane, qsplit=2, compacted=False)),
+        (129, 2369, dict(lane, qsplit=1, compacted=True, soa=False, lds_cap=2369)),
+        (130, 2369, dict(lane, qsplit=1, compacted=True)),
+        (256, 2369, dict(lane, qsplit=1, compacted=True)),
+        (129, 6144, dict(lane, qsplit=1, compacted=True, soa=False, lds_cap=6144)),
+        (129, 6145, dict(lane, qsplit=1, compacted=True, soa=True, lds_cap=6145)),
+        (129, 10752, dict(lane, qsplit=1, compacted=True, soa=True, lds_cap=10752)),
+        (129, 10753, dict(lane, qsplit=1, compacted=True, soa=True, lds_cap=10752)),
+        (129, 16384, dict(lane, qsplit=1, compacted=True, soa=True, lds_cap=10752)),
+        (129, 16385, dict(strip_path=False, group_mode=False, soa=False, qsplit=0, lds_cap=0, compacted=False)),
+        (1, 16385, dict(strip_path=False, compacted=False)),
+        (129, 0, dict(strip_path=False, compacted=False)),
+    ]
+    for n, mx, want in rows:
+        p = ssf.register_plan(n, mx)
+        assert {k: p[k] for k in want} == want, (n, mx, p)
+    # point-to-line blocks: never compacted, the rest of the launch unchanged
+    for n, mx in ((1, 2369), (17, 1024), (129, 2369), (256, 900), (129, 16384), (129, 16385)):
+        p, e = ssf.register_plan(n, mx), ssf.register_plan(n, mx, with_edges=True)
+        assert not e["compacted"] and e == dict(p, compacted=False), (n, mx, e)
+    L = _abi.lib()
+    out = _abi.LaunchPlan()
+    assert L.ssf_register_plan(129, 2369, 0, C.byref(out)) == _abi.SSF_OK and out.compacted == 1
+    assert L.ssf_register_plan(0, 2369, 0, C.byref(out)) == _abi.SSF_E_ARG
+    assert L.ssf_register_plan(-1, 2369, 0, C.byref(out)) == _abi.SSF_E_ARG
+    assert L.ssf_register_plan(129, -1, 0, C.byref(out)) == _abi.SSF_E_ARG
+    assert L.ssf_register_plan(129, 2369, 0, None) == _abi.SSF_E_ARG
+    with pytest.raises(ValueError):
+        ssf.register_plan(0, 100)
+
+
 def test_no_cpu_fallback_in_product_package():
     """the product package never imports the oracle"""
     pkg = os.path.join(REPO, "ssf-slam_amd")

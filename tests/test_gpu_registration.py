@@ -132,8 +132,10 @@ def test_plane_table_rank_walk_cases(oracle, dev):
 def test_nan_warm_start_association_stays_in_frame(dev):
     """A NaN warm start (an ill-conditioned link of a chain) makes every query point NaN: no
     candidate wins.  Both association modes -- the group mode of launches of <= 16 pairs and the
-    lane mode of big launches -- fall back to the last frame's first staged point (the
-    group mode used index -1, reading the neighbouring frame's records), and the call returns."""
+    lane mode split over two work-groups per pair (20 pairs: records in query order, not
+    compacted) -- fall back to the last frame's first staged point (the group mode
+    used index -1, reading the neighbouring frame's records), and the call returns.  The
+    compacted lane mode of big launches: test_gpu_compacted.py::test_compacted_nan_warm_start."""
     import ssf
     fe = ssf.Frontend(64, device=dev.index)
     clouds = [frame(0, 2, n_az=600)[0], frame(0, 3, n_az=600)[0]]
@@ -142,6 +144,9 @@ def test_nan_warm_start_association_stays_in_frame(dev):
     m_last = int(pb.count[0])
     o1, m1 = int(pb.h_off[1]), int(pb.count[1])
     got = []
+    assert ssf.register_plan(1, pb.max_points)["group_mode"]
+    plan = ssf.register_plan(20, pb.max_points)
+    assert not plan["group_mode"] and plan["qsplit"] == 2 and not plan["compacted"], plan
     for n_pairs in (1, 20):
         last, curr = _sub(pb, [0] * n_pairs), _sub(pb, [1] * n_pairs)
         pose = torch.full((n_pairs, 7), float("nan"), dtype=torch.float64, device=dev)
@@ -155,17 +160,21 @@ def test_nan_warm_start_association_stays_in_frame(dev):
 
 @pytest.mark.parametrize("solver,iters", [("gn", 10), ("ceres_lm", 8)])
 def test_compacted_records_same_bits(dev, solver, iters):
-    """Big launches (> 16 pairs, one association work-group per pair) hand the solve compacted
-    records in rank order and the solve streams them into LDS inside its first evaluation; a
-    single-pair launch (group-mode association) writes records in query order and the solve
-    compacts them itself.  Both feed the evaluations the same records in the same order: poses,
-    per-step logs and correspondence counts must be bit-identical."""
+    """A launch of 17 pairs takes the lane-mode association split over three work-groups per
+    pair (qsplit = min(8, 256 / 17, ceil(2369 / 1024)) = 3): records in query order, compacted by
+    the solve's ballot pass, as in a single-pair launch (group-mode association).  Both feed the
+    evaluations the same records in the same order: poses, per-step logs and correspondence
+    counts must be bit-identical.  (The records the association compacts itself -- qsplit == 1 --
+    are test_gpu_compacted.py's.)"""
     import ssf
     fe = ssf.Frontend(64, device=dev.index, solver=solver, max_iter=iters)
     # 17 pairs of one sequence (distinct current frames: the records live at their offsets)
     P = 17
     clouds = [frame(3, k, n_az=900)[0] for k in range(P + 1)]
     pb = _planes(fe, dev, clouds)
+    plan = ssf.register_plan(P, pb.max_points)
+    assert not plan["group_mode"] and plan["qsplit"] == 3 and not plan["compacted"], plan
+    assert ssf.register_plan(1, pb.max_points)["group_mode"]
     table = fe.plane_table(pb)
     rng = np.random.default_rng(11)
     sel = [(k, k + 1) for k in range(P)]
@@ -202,15 +211,19 @@ def test_compacted_records_same_bits(dev, solver, iters):
 
 
 def test_compacted_records_edge_pairs(dev):
-    """The compacted-record path's edge cases inside one big launch (> 16 pairs): a pair whose
-    last frame has <= 10 plane points (:158, skipped, count 0), a pair with an empty current
-    frame, and a pair whose current frame is cut to 3 points -- every pair's pose, log and count
-    bit-identical to its own single-pair launch (group-mode association, solve-side compaction)."""
+    """Edge cases inside one lane-mode launch (18 pairs, three work-groups per pair, solve-side
+    compaction): a pair whose last frame has <= 10 plane points (:158, skipped, count -1), a pair
+    with an empty current frame, and a pair whose current frame is cut to 3 points -- every
+    pair's pose, log and count bit-identical to its own single-pair launch (group-mode
+    association, solve-side compaction too).  The same cases on the compacted-record path:
+    test_gpu_compacted.py::test_compacted_edge_pairs."""
     import ssf
     fe = ssf.Frontend(64, device=dev.index, solver="gn", max_iter=10)
     P = 18
     clouds = [frame(4, k, n_az=900)[0] for k in range(P + 1)]
     pb = _planes(fe, dev, clouds)
+    plan = ssf.register_plan(P, pb.max_points)
+    assert not plan["group_mode"] and plan["qsplit"] == 3 and not plan["compacted"], plan
     table = fe.plane_table(pb)
     init = torch.tensor([[0.0, 0.0, 0.001, 1.0, 0.8, 0.0, 0.0]] * P, dtype=torch.float64, device=dev)
     init[:, :4] /= torch.linalg.norm(init[:, :4], dim=1, keepdim=True)
