@@ -90,15 +90,16 @@ def build_examples() -> list:
 
 
 def build_diag() -> str:
-    """Diagnostic library (phase stamps in k_mask_pose, -DSSF_MASK_STAMPS) for
-    tools/diag_mask_phases.py; never loaded by the product path unless SSF_LIB points at it."""
+    """Diagnostic library (phase stamps in k_mask_pose, -DSSF_MASK_STAMPS, and in
+    k_plane_table_sorted, -DSSF_TABLE_STAMPS) for tools/diag_mask_phases.py and
+    tools/diag_table_phases.py; never loaded by the product path unless SSF_LIB points at it."""
     out = os.path.join(OUT_DIR, "libssf_frontend_diag.so")
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ_DIR, src.replace(".hip", "_diag.o"))
         extra = {"mask_pose.hip": ["-DSSF_MASK_STAMPS"], "mask_pose_f64.hip": ["-DSSF_MASK_STAMPS"],
-                 "registration.hip": ["-DSSF_TABLE_STAMPS", "-DSSF_ASSOC_STAMPS"]}.get(src, [])
+                 "registration.hip": ["-DSSF_TABLE_STAMPS"]}.get(src, [])
         subprocess.run([HIPCC, *FLAGS, *FILE_FLAGS.get(src, []), *extra, "-c", s, "-o", o], check=True)
         objs.append(o)
     subprocess.run([HIPCC, *FLAGS, "-shared", *objs, "-o", out], check=True)

@@ -559,7 +559,7 @@ int32_t ssf_register_plan(int32_t n_pairs, int64_t max_plane_points, int32_t wit
     if (!out || n_pairs < 1 || max_plane_points < 0) return SSF_E_ARG;
     const ssf::RegisterPlan r = ssf::register_plan(n_pairs, max_plane_points, with_edges != 0);
     out->strip_path = r.strips;
-    out->group_mode = r.coop || r.bigc;
+    out->group_mode = r.coop;
     out->soa = r.soa;
     out->qsplit = r.qsplit;
     out->lds_cap = r.lds_cap;

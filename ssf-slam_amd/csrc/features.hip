@@ -42,9 +42,6 @@ namespace ssf {
 // where the second id starts (float; and as the exact double for the double chain), id below,
 // id from there}.  The device computes the ratio exactly as the reference and does ONE table
 // lookup and one compare: no atan on the device at all.
-#ifndef SSF_FEAT_EXACT_ID
-#define SSF_FEAT_EXACT_ID 0                      // A/B: the exact ratio for every point
-#endif
 constexpr int kRingCells = 256;
 constexpr int kRingChainFloat = SSF_RING_CHAIN_FLOAT, kRingChainDouble = SSF_RING_CHAIN_DOUBLE;
 struct RingCell {
@@ -96,7 +93,6 @@ SSF_DEV int ring_id_exact(float x, float y, float z, float r0, float inv, const 
 SSF_DEV int ring_id_table(float x, float y, float z, float r0, float inv, const RingCell* T,
                           const RingTable* __restrict__ rt) {
     const float r2 = x * x + y * y;
-    if (SSF_FEAT_EXACT_ID) return ring_id_exact(x, y, z, r0, inv, T, rt);   // A/B: no fast path
     const float ra = z * __builtin_amdgcn_rsqf(r2);
     int ci = (int)((ra - r0) * inv);
     ci = min(max(ci, 0), kRingCells - 1);
@@ -703,21 +699,6 @@ __global__ __launch_bounds__(kSelThreads) void k_select(const float* __restrict_
 // stencils, rare for azimuth-ordered scans -- through the chunk-major index, the same taps in the
 // same order.  Every write of k_feat_chunk is a whole, aligned, contiguous run (no per-row
 // scatter); the greedy of k_feat_select walks each row as its sequence of (chunk, row) segments.
-#ifndef SSF_FEAT_PACKED
-#define SSF_FEAT_PACKED 0                        // packed-f32 stencil (A/B, see k_feat_chunk)
-#endif
-#ifndef SSF_FEAT_ZONES
-#define SSF_FEAT_ZONES 0                         // A/B: one-zone steps count without masks (spills: slower)
-#endif
-#ifndef SSF_FEAT_REGULAR
-#define SSF_FEAT_REGULAR 1                       // k_feat_chunk_reg for regular windows (A/B: 0)
-#endif
-#ifndef SSF_SEL_CUT
-#define SSF_SEL_CUT 0                            // timing tools only: stop k_feat_select after phase 1..4
-#endif
-#ifndef SSF_FEAT_CUT
-#define SSF_FEAT_CUT 0                           // timing tools only: stop k_feat_chunk after phase 1..4
-#endif
 #ifndef SSF_FEAT_WAVES
 #define SSF_FEAT_WAVES 5                         // k_feat_chunk waves per SIMD (launch bound)
 #endif
@@ -727,7 +708,7 @@ constexpr int kFeatWords = kBinChunk / 64;       // 64-bit words per plane and c
 constexpr uint8_t kFlP = 1, kFlU = 2, kFlE = 4;
 // per (frame, chunk) block flag of the single-read stage: which kernel did the chunk and where
 // k_feat_select finds a selected point's chunk position
-//   kIrrRegular  k_feat_wave_reg / k_feat_chunk_reg: 64 x own column + the row's lane (lane map)
+//   kIrrRegular  k_feat_wave_reg: 64 x own column + the row's lane (lane map)
 //   kIrrGeneral  not done yet -> k_feat_chunk_flagged, which writes the u16 position of every slot
 //   kIrrRun      k_feat_wave_run: the row's run start (u16 at the chunk's first 64 index entries) + o
 //   kIrrRunIdx   k_feat_wave_run with the debug outputs: the u16 position of every slot
@@ -750,17 +731,16 @@ static_assert(kTileE >= kWin + kMaxRows, "k_feat_chunk's tile holds the window p
 SSF_DEV int idl_sw(int p) { return p ^ (((p >> 6) & 15) << 2); }
 SSF_DEV int fll_sw(int p) { return p ^ (((p >> 7) & 7) << 2); }
 
-// The chunk's outputs from LDS (k_feat_chunk, k_feat_chunk_reg): the u16 chunk positions in
+// The chunk's outputs from LDS (k_feat_chunk): the u16 chunk positions in
 // own-tile order as whole 8-byte runs (idl, swizzled by idl_sw), and the candidate / unresolved
 // (/ edge) bit planes packed from the flag bytes (fll, swizzled by fll_sw).
 template <bool kEdge>
 SSF_DEV void feat_chunk_out(int tid, int f, int c, int n_chunks, const int64_t* __restrict__ frame_off,
                             int clen, int no, const uint16_t* idl, const uint8_t* fll,
-                            uint16_t* __restrict__ gidx, uint64_t* __restrict__ gbits, bool write_idx = true) {
+                            uint16_t* __restrict__ gidx, uint64_t* __restrict__ gbits) {
     uint16_t* gi = gidx + idx_base(frame_off, f) + (int64_t)c * kBinChunk;   // 4 KiB aligned run
-    if (write_idx)                                            // uniform
-        for (int k = tid; 4 * k < clen; k += kCurvNT)         // 8-byte stores (4 slots)
-            *reinterpret_cast<uint2*>(gi + 4 * k) = *reinterpret_cast<const uint2*>(idl + 4 * (k ^ ((k >> 4) & 15)));
+    for (int k = tid; 4 * k < clen; k += kCurvNT)             // 8-byte stores (4 slots)
+        *reinterpret_cast<uint2*>(gi + 4 * k) = *reinterpret_cast<const uint2*>(idl + 4 * (k ^ ((k >> 4) & 15)));
     uint64_t* gb = gbits + ((int64_t)f * n_chunks + c) * (kFeatPlanes * kFeatWords);
     constexpr int kPl = kEdge ? 3 : 2;
     if (tid < kPl * kFeatWords) {
@@ -854,9 +834,6 @@ SSF_DEV void feat_chunk_block(int64_t lb, const float* __restrict__ pts, int str
         const int id = ring_id_table(px[st], py[st], pz[st], r0, rinv, rcell, rtab);   // every lane: no branch
         idr[st] = in ? id : -1;
     }
-#if SSF_FEAT_CUT == 1                                         // timing only (tools): ring ids
-    { int acc = 0; for (int st = 0; st < kWinQ; ++st) acc += idr[st]; if (acc == 0x7fffffff) cnt[0] = acc; return; }
-#endif
     // rank among same-row points (the k_bin_curv ranking: per-row lane words, waves in order).
     // Every lane of a row computes the same new counter word and writes it (and clears the lane
     // word): the wave's LDS instructions complete in order, so all reads of the step precede
@@ -874,14 +851,9 @@ SSF_DEV void feat_chunk_block(int64_t lb, const float* __restrict__ pts, int str
         const int hel = __builtin_amdgcn_readfirstlane(min(64, max(0, he - s0)));
         const int rin = __popcll(m & lanemask_lt());
         const uint64_t pm = (uint64_t)__popcll(m);
-        uint64_t inc;
-        if (SSF_FEAT_ZONES && (hbl == 0 || hbl == 64) && (hel == 0 || hel == 64)) {   // uniform: one zone
-            inc = pm * (1ull + (hbl ? 1ull << 16 : 0ull) + (hel ? 1ull << 32 : 0ull));
-        } else {                                              // the (at most two) boundary steps
-            const uint64_t hm = hbl >= 64 ? ~0ull : ((1ull << hbl) - 1ull);   // lanes before the chunk
-            const uint64_t om = hel >= 64 ? ~0ull : ((1ull << hel) - 1ull);   // lanes before its end
-            inc = pm + ((uint64_t)__popcll(m & hm) << 16) + ((uint64_t)__popcll(m & om) << 32);
-        }
+        const uint64_t hm = hbl >= 64 ? ~0ull : ((1ull << hbl) - 1ull);   // lanes before the chunk
+        const uint64_t om = hel >= 64 ? ~0ull : ((1ull << hel) - 1ull);   // lanes before its end
+        const uint64_t inc = pm + ((uint64_t)__popcll(m & hm) << 16) + ((uint64_t)__popcll(m & om) << 32);
         wrun[w][rs] = old + inc;
         __hip_atomic_store(gm, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         idr[st] = (id & 0xff) | (((int)(old & 0xffffu) + rin) << 8);
@@ -919,9 +891,6 @@ SSF_DEV void feat_chunk_block(int64_t lb, const float* __restrict__ pts, int str
         if (r == 63) { ntot = incl + n_rows; nown = oincl; }  // tile entries incl. one pad per row
     }
     __syncthreads();
-#if SSF_FEAT_CUT == 2                                         // timing only: + ranking, row scan
-    { int acc = ntot; for (int st = 0; st < kWinQ; ++st) acc += idr[st]; if (acc == 0x7fffffff) cnt[0] = acc; return; }
-#endif
     const int nt = ntot;
     const int64_t cm = fb + (int64_t)c * kBinChunk;           // chunk-major base (curvature)
     // ---- place: tile slot of every window point, own-tile slot + position of every own point
@@ -955,47 +924,6 @@ SSF_DEV void feat_chunk_block(int64_t lb, const float* __restrict__ pts, int str
         }
     }
     __syncthreads();
-#if SSF_FEAT_CUT == 3                                         // timing only: + place
-    { int acc = 0; for (int st = 0; st < kWinQ; ++st) acc += loc[st]; if (acc == 0x7fffffff) cnt[0] = acc; return; }
-#endif
-#if SSF_FEAT_PACKED
-    // ---- curvature of this thread's kCE tile entries, one coordinate at a time, entries i and
-    // i + kCE / 2 side by side in packed f32 (v_pk_add_f32 / v_pk_mul_f32: two IEEE operations,
-    // the same rounding as two scalar ones): tap k of the pair is (t[k0 + i + k], t[k0 + i + 6 + k]),
-    // one ds_read2_b32 -- the sums keep the reference's left-to-right order (frameFeature.cpp:88-97)
-    static_assert(kCE == 12, "the packed stencil pairs entries i and i + 6");
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const int k0 = kCE * tid;
-    f2 v2[kCE / 2];
-    auto coord = [&](bool first) {
-        const float* t = sc + k0 + 3;                         // tap 0 of entry 0 (centre at + 5)
-        f2 P[kCE / 2 + 10];                                   // P[j] = (t[j], t[j + 6])
-#pragma unroll
-        for (int j = 0; j < kCE / 2 + 10; ++j) P[j] = f2{t[j], t[j + kCE / 2]};
-#pragma unroll
-        for (int i = 0; i < kCE / 2; ++i) {
-            f2 acc = P[i] + P[i + 1];
-#pragma unroll
-            for (int k = 2; k < 11; ++k) acc = (k == 5) ? acc - f2{10.0f, 10.0f} * P[i + 5] : acc + P[i + k];
-            const f2 sq = acc * acc;
-            v2[i] = first ? sq : v2[i] + sq;
-        }
-    };
-    coord(true);
-    __syncthreads();
-#pragma unroll
-    for (int st = 0; st < kWinQ; ++st) sc[kTilePad + loc[st]] = py[st];
-    __syncthreads();
-    coord(false);
-    __syncthreads();
-#pragma unroll
-    for (int st = 0; st < kWinQ; ++st) sc[kTilePad + loc[st]] = pz[st];
-    __syncthreads();
-    coord(false);
-    float v[kCE];
-#pragma unroll
-    for (int i = 0; i < kCE / 2; ++i) { v[i] = v2[i].x; v[i + kCE / 2] = v2[i].y; }
-#else
     // ---- curvature of this thread's kCE tile entries, one coordinate at a time (k_bin_curv)
     const int k0 = kCE * tid;
     float v[kCE];
@@ -1031,10 +959,6 @@ SSF_DEV void feat_chunk_block(int64_t lb, const float* __restrict__ pts, int str
 #pragma unroll
         for (int i = 0; i < kCE; ++i) v[i] = v[i] + d0[i] * d0[i];
     }
-#endif
-#if SSF_FEAT_CUT == 4                                         // timing only: + stencils
-    { float acc = 0.f; for (int i = 0; i < kCE; ++i) acc += v[i]; if (acc == 1234.5f) cnt[0] = 1; return; }
-#endif
     uint16_t mt[kCE];
 #pragma unroll
     for (int i = 0; i < kCE; i += 4) {                        // k0 + kCE <= kTileE: 8-byte reads
@@ -1074,7 +998,7 @@ __global__ __launch_bounds__(kCurvNT, SSF_FEAT_WAVES) void k_feat_chunk(SSF_FC_P
     feat_chunk_block<kDebug, kEdge>(lb, SSF_FC_ARGS);
 }
 
-// after k_feat_chunk_reg: only the blocks it flagged.  A work-group reads the flags of 16
+// after k_feat_wave_reg / k_feat_wave_run: only the blocks they flagged.  A work-group reads the flags of 16
 // consecutive blocks in one 16-byte load and does the flagged ones in turn, so a launch of
 // regular frames is nblk / 16 work-groups that return at once (one work-group per block cost
 // ~9 us to drain for 15 k blocks)
@@ -1100,187 +1024,16 @@ __global__ __launch_bounds__(kCurvNT, SSF_FEAT_WAVES) void k_feat_chunk_flagged(
 #undef SSF_FC_ARGS
 #undef SSF_FC_PARAMS
 
-// k_feat_chunk_reg: the same outputs for REGULAR windows, the common layout of a 64-beam scan in
-// azimuth order (the reference's driver order; the bench's synthetic scans): the window is whole
-// columns of 64 points, each column holds every row once, and lane l of every column is the same
-// row.  Then a row's points in the window are one lane's column sequence -- rank = column, the
-// own-tile slot is row x own columns + (column - first own column), and the 11 taps of a stencil
-// are that lane's columns c - 5 .. c + 5 -- so there is no ranking, no placement and no
-// row-grouped tile: each coordinate goes through a column-major LDS image (conflict-free 4-byte
-// stores and loads), the lane's 21 columns into registers, tap11 in the reference's order.
-// Covered stencils, unresolved points, flags, positions and counts are exactly those of
-// k_feat_chunk (same taps, same order, same rounding).  A window that is not regular (masked
-// points, a ragged frame end, a point without a row, another order) is flagged, and k_feat_chunk,
-// launched after it, does exactly the flagged blocks.
-#ifndef SSF_FEAT_REG_LDS
-#define SSF_FEAT_REG_LDS 0                       // k_feat_chunk_reg: halo columns from global (A/B 1: through LDS, 0.155 vs 0.147 ms)
-#endif
-#ifndef SSF_FEAT_REG_WAVES
-#define SSF_FEAT_REG_WAVES 5                     // k_feat_chunk_reg waves per SIMD (launch bound)
-#endif
-template <bool kDebug, bool kEdge>
-__global__ __launch_bounds__(kCurvNT, SSF_FEAT_REG_WAVES) void k_feat_chunk_reg(
-    const float* __restrict__ pts, int stride, const int64_t* __restrict__ frame_off, int n_frames,
-    int n_rows, int n_chunks, int row_start, int row_end, float plane_min, float edge_min,
-    const RingTable* __restrict__ rtab, int32_t* __restrict__ cnt, uint16_t* __restrict__ gidx,
-    uint64_t* __restrict__ gbits, float* __restrict__ curv_cm, uint8_t* __restrict__ irregular,
-    uint8_t* __restrict__ lanemap) {
-    __shared__ __attribute__((aligned(16))) float sc[kWin];     // one coordinate, column-major
-    __shared__ __attribute__((aligned(16))) uint16_t idl[kBinChunk + 4];
-    __shared__ __attribute__((aligned(16))) uint8_t fll[kBinChunk];
-    __shared__ int lid[kMaxRows];
-    __shared__ unsigned long long lrows;
-    static_assert(kWin % 64 == 0 && 64 * kCurvNW * kWinQ >= kWin, "columns");
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t nblk = (int64_t)n_chunks * n_frames;        // XCD-aware logical block
-    const int64_t q8 = (nblk + 7) / 8;
-    const int64_t lb = (int64_t)(blockIdx.x % 8) * q8 + blockIdx.x / 8;
-    if (lb >= nblk) return;
-    const int f = (int)(lb / n_chunks), c = (int)(lb - (int64_t)f * n_chunks);
-    const int64_t fb = frame_off[f], e = frame_off[f + 1];
-    const int64_t s = fb + (int64_t)c * kBinChunk;
-    if (s >= e) {                                             // uniform: no chunk here at all
-        if (tid == 0) irregular[lb] = 0;
-        return;
-    }
-    const int64_t t = min(e, s + (int64_t)kBinChunk);
-    const int64_t ws = max(fb, s - (int64_t)kCurvHalo), we = min(e, t + (int64_t)kCurvHalo);
-    const int L = (int)(we - ws), hb = (int)(s - ws), he = (int)(t - ws);
-    if (((L | hb | he) & 63) != 0) {                          // uniform: not whole columns
-        if (tid == 0) irregular[lb] = 1;
-        return;
-    }
-    const int ncols = L >> 6, c_hb = hb >> 6, own_cols = (he - hb) >> 6;
-    const int cpw = (ncols + kCurvNW - 1) / kCurvNW;          // columns per wave (<= kWinQ)
-    const int cw0 = w * cpw, nst = max(0, min(cpw, ncols - cw0));   // uniform
-    float px[kWinQ], py[kWinQ], pz[kWinQ];
-    // column col, lane l at pw + col x 64 stride (uniform: scalar) + l x stride (once per lane):
-    // no per-load integer multiply
-    const float* pw = pts + ws * stride + lane * stride;
-    const int cstride = 64 * stride;
-#pragma unroll
-    for (int st = 0; st < kWinQ; ++st) {                      // every load first (clamped)
-        const float* pp = pw + min(cw0 + st, ncols - 1) * cstride;
-        px[st] = pp[0]; py[st] = pp[1]; pz[st] = pp[2];
-    }
-#if !SSF_FEAT_REG_LDS
-    // the 5 columns on each side of the wave's 11 (stencil taps of its edge columns) straight
-    // from global memory (L2: neighbouring waves load them as their own), in flight across the
-    // ring ids and the regularity check
-    float hx[10], hy[10], hz[10];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        const int col = k < 5 ? max(cw0 - 5 + k, 0) : min(cw0 + kWinQ + k - 5, ncols - 1);
-        const float* pp = pw + col * cstride;
-        hx[k] = pp[0]; hy[k] = pp[1]; hz[k] = pp[2];
-    }
-#endif
-    if (tid == 0) lrows = 0ull;
-    // the row of the lane's first column (frameFeature.cpp:57-73 by the exact table, read from
-    // L2), then every column's point checked INSIDE that row's ratio interval with the fast ratio
-    // z * rsq(x^2 + y^2): 1e-6 (relative) clear of both ends, so the correctly rounded ratio, and
-    // with it the reference's id, is that row too; a point near an end (a few in a million)
-    // makes the window irregular
-    const int mine = ring_id_table(px[0], py[0], pz[0], rtab->r0, rtab->inv, rtab->cell, rtab);
-    const int mr = mine & (kMaxRows - 1);
-    const float rlo = rtab->rlo[mr], rhi = rtab->rhi[mr];
-    int ok = mine >= 0 && mine < kMaxRows;
-    // the columns' ratios into one 0 / 1 word first (no ratio kept live across the loop)
-    uint32_t inb = 0;
-#pragma unroll
-    for (int st = 0; st < kWinQ; ++st) {
-        const float r2 = px[st] * px[st] + py[st] * py[st];
-        const float ra = pz[st] * __builtin_amdgcn_rsqf(r2);
-        const float m = 1e-6f * fmaxf(1.0f, fabsf(ra));
-        const bool in = ra >= rlo + m && ra < rhi - m && r2 > 1e-30f && r2 < 1e30f;
-        inb |= (uint32_t)in << st;
-    }
-    const uint32_t need = nst >= 32 ? ~0u : ((1u << nst) - 1u);
-    ok &= (int)((inb & need) == need);
-    if (w == 0) lid[lane] = mine;
-    __syncthreads();
-    const int row = lid[lane];
-    ok &= (int)(nst == 0) | (int)(mine == row);
-    ok &= (int)(row >= 0);
-    if (w == 0 && row >= 0)
-        __hip_atomic_fetch_or(&lrows, 1ull << row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __syncthreads();
-    ok &= (int)(lrows == ~0ull);                              // every row once per column
-    if (!__syncthreads_and(ok)) {                             // uniform: the general kernel's block
-        if (tid == 0) irregular[lb] = 1;
-        return;
-    }
-    if (tid == 0) irregular[lb] = 0;
-    // the chunk's row -> lane map (64 B): k_feat_select derives a selected point's chunk position
-    // from it (64 x own column + lane) instead of gathering it from the u16 index, which this
-    // kernel then writes only for the debug outputs
-    if (w == 0) lanemap[lb * kMaxRows + row] = (uint8_t)lane;
-    float v[kWinQ];
-#if SSF_FEAT_REG_LDS
-    auto coord = [&](const float (&P)[kWinQ], bool first) {
-#pragma unroll
-        for (int st = 0; st < kWinQ; ++st)
-            if (st < nst) sc[(cw0 + st) * 64 + lane] = P[st];
-        __syncthreads();
-        float ext[kWinQ + 10];                                // columns cw0 - 5 .. cw0 + kWinQ + 4
-#pragma unroll
-        for (int k = 0; k < kWinQ + 10; ++k) ext[k] = sc[min(max(cw0 - 5 + k, 0), ncols - 1) * 64 + lane];
-#pragma unroll
-        for (int st = 0; st < kWinQ; ++st) {
-            const float d = tap11(ext + st);
-            v[st] = first ? d * d : v[st] + d * d;            // ((dX dX + dY dY) + dZ dZ)
-        }
-        __syncthreads();                                      // before the next coordinate's stores
-    };
-    coord(px, true);
-    coord(py, false);
-    coord(pz, false);
-#else
-    auto coord = [&](const float (&P)[kWinQ], const float (&H)[10], bool first) {
-        float ext[kWinQ + 10];                                // columns cw0 - 5 .. cw0 + kWinQ + 4
-#pragma unroll
-        for (int k = 0; k < 5; ++k) { ext[k] = H[k]; ext[kWinQ + 5 + k] = H[5 + k]; }
-#pragma unroll
-        for (int st = 0; st < kWinQ; ++st) ext[5 + st] = P[st];   // px[st] is column cw0 + st (clamped)
-#pragma unroll
-        for (int st = 0; st < kWinQ; ++st) {
-            const float d = tap11(ext + st);
-            v[st] = first ? d * d : v[st] + d * d;            // ((dX dX + dY dY) + dZ dZ)
-        }
-    };
-    coord(px, hx, true);
-    coord(py, hy, false);
-    coord(pz, hz, false);
-#endif
-    const bool row_in = row >= row_start && row < n_rows - row_end;
-    const int64_t cm = fb + (int64_t)c * kBinChunk;           // chunk-major base (curvature)
-#pragma unroll
-    for (int st = 0; st < kWinQ; ++st) {
-        const int col = cw0 + st;
-        if (st < nst && col >= c_hb && col < c_hb + own_cols) {
-            const int p = row * own_cols + (col - c_hb);
-            const bool covered = col >= 5 && col < ncols - 5;
-            uint8_t fl = row_in ? kFlU : (uint8_t)0;
-            if (row_in && covered) {
-                const uint8_t cf = cand_flags(true, true, v[st], plane_min, kEdge, edge_min);
-                fl = (uint8_t)((cf & 1) ? kFlP : 0) | (uint8_t)((cf & 2) ? kFlE : 0);
-            }
-            idl[idl_sw(p)] = (uint16_t)(64 * (col - c_hb) + lane);
-            fll[fll_sw(p)] = fl;
-            if (kDebug && curv_cm) curv_cm[cm + p] = (row_in && covered) ? v[st] : 0.0f;
-        }
-    }
-    if (tid < kMaxRows) cnt[((int64_t)f * (n_chunks + 1) + c) * kMaxRows + tid] = own_cols;
-    __syncthreads();
-    feat_chunk_out<kEdge>(tid, f, c, n_chunks, frame_off, (int)(t - s), kMaxRows * own_cols, idl, fll,
-                          gidx, gbits, kDebug);
-}
-
-// k_feat_wave_reg: k_feat_chunk_reg's outputs with ONE WAVE per chunk (round 4).  In a regular
-// window lane l of every column is the same row, so a chunk's whole stencil work is one lane's
-// column sequence and needs no other wave: a work-group is kCurvNW independent chunks with no
-// barrier at all.  Each wave loads the ring table into registers (lane l: cells 4l .. 4l + 3,
+// k_feat_wave_reg: k_feat_chunk's outputs for REGULAR windows with ONE WAVE per chunk (round 4).
+// Regular is the common layout of a 64-beam scan in azimuth order (the reference's driver order;
+// the bench's synthetic scans): the window is whole columns of 64 points, each column holds every
+// row once, and lane l of every column is the same row.  Then a row's points in the window are
+// one lane's column sequence -- rank = column, the own-tile slot is row x own columns + (column -
+// first own column), and the 11 taps of a stencil are that lane's columns c - 5 .. c + 5 -- so
+// there is no ranking, no placement and no row-grouped tile, a chunk's whole stencil work needs
+// no other wave, and a work-group is kCurvNW independent chunks with no barrier at all.  A window
+// that is not regular (masked points, a ragged frame end, a point without a row, another order)
+// is flagged for the kernels launched after this one.  Each wave loads the ring table into registers (lane l: cells 4l .. 4l + 3,
 // rlo / rhi of row l; a lookup is a lane permute), then the chunk's 32 own columns and the 5 on
 // each side (42 column loads of 768 B, streamed in blocks of kWB own columns, see stream below),
 // checks regularity, evaluates every covered stencil from registers and builds the
@@ -1291,9 +1044,6 @@ __global__ __launch_bounds__(kCurvNT, SSF_FEAT_REG_WAVES) void k_feat_chunk_reg(
 // reaches them, and they cannot change whether one is covered (a covered own point's 5 row
 // neighbours on each side lie in the checked columns, which hold its row exactly once each), so
 // the outputs are those of k_feat_chunk on every window this kernel calls regular.
-#ifndef SSF_FEAT_WAVE_REG
-#define SSF_FEAT_WAVE_REG 1                      // k_feat_wave_reg instead of k_feat_chunk_reg (A/B: 0)
-#endif
 #ifndef SSF_FEAT_WAVE_WAVES
 #define SSF_FEAT_WAVE_WAVES 4                    // k_feat_wave_reg waves per SIMD (launch bound; 126 VGPRs)
 #endif
@@ -1387,8 +1137,8 @@ __global__ __launch_bounds__(kCurvNT, (kDebug || kEdge) ? 3 : SSF_FEAT_WAVE_WAVE
     const int64_t cm = fb + (int64_t)c * kBinChunk;           // chunk-major base (curvature)
     uint16_t* gi = gidx + idx_base(frame_off, f) + (int64_t)c * kBinChunk;
     // every real column's point inside the row's ratio interval, clear of both ends by the row's
-    // margin 1e-6 max(1, |rlo|, |rhi|) -- at least k_feat_chunk_reg's per-point 1e-6 max(1, |ra|)
-    // for any ra inside, so it accepts a subset of what that check accepts -- folded into the
+    // margin 1e-6 max(1, |rlo|, |rhi|) -- at least ring_id_table's per-point 1e-6 max(1, |ra|)
+    // for any ra inside, so the fast ratio's row is the exact one -- folded into the
     // bounds once per lane (rlo / rhi below): per column one rsq, one multiply, four compares
     auto check_col = [&](int k) {
         const f2 q2 = XY[k] * XY[k];
@@ -1560,9 +1310,6 @@ __global__ __launch_bounds__(kCurvNT, (kDebug || kEdge) ? 3 : SSF_FEAT_WAVE_WAVE
 // moves for runs in ascending row order without gaps), and k_feat_select finds a point at its
 // row's run start (u16, the chunk's first 64 index entries) + its offset.  A chunk with a row in
 // two runs, or more than kRunMax runs, is left to k_feat_chunk (kIrrGeneral).
-#ifndef SSF_FEAT_WAVE_RUN
-#define SSF_FEAT_WAVE_RUN 1                      // k_feat_wave_run for the non-regular chunks (A/B: 0)
-#endif
 #ifndef SSF_FEAT_RUN_WAVES
 #define SSF_FEAT_RUN_WAVES 8                     // k_feat_wave_run waves per SIMD (launch bound)
 #endif
@@ -1572,12 +1319,6 @@ constexpr int kRunMax = 64;                      // runs (and gaps) logged per c
 #define SSF_FEAT_RUN_PF 3                        // registers in flight per wave (r5ao: 3 0.0955 vs 4 0.0966 ms)
 #endif
 constexpr int kRunPF = SSF_FEAT_RUN_PF;
-#ifndef SSF_FEAT_RUN_SOFF
-#define SSF_FEAT_RUN_SOFF 0                      // A/B: the register step as the buffer load's SGPR offset
-#endif
-#ifndef SSF_FEAT_RUN_BALLOT1
-#define SSF_FEAT_RUN_BALLOT1 0                   // A/B: the interior test as one ballot of a combined predicate
-#endif
 
 SSF_DEV float dpp_shr1(float v) {                // lane l <- lane l - 1 (lane 0 <- 0)
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xf, 0xf, true));
@@ -1676,12 +1417,7 @@ __global__ __launch_bounds__(kCurvNT, kDebug ? 2 : SSF_FEAT_RUN_WAVES) void k_fe
     const uint32_t sb = (uint32_t)stride * 4u;
     const uint32_t voff0 = (uint32_t)(q0 + lane) * sb, vstep = (uint32_t)kRunStep * sb;
     auto load_reg = [&](int k, float& x, float& y, float& z, uint32_t& kp) {
-#if SSF_FEAT_RUN_SOFF
-        // the register's step as the scalar offset (SGPR): no vector add per load
-        const i3v v = __builtin_amdgcn_raw_buffer_load_b96(prs, voff0, (int)((uint32_t)k * vstep), 0);
-#else
         const i3v v = __builtin_amdgcn_raw_buffer_load_b96(prs, voff0 + (uint32_t)k * vstep, 0, 0);
-#endif
         x = __int_as_float(v.x); y = __int_as_float(v.y); z = __int_as_float(v.z);
         kp = keep ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(krs, (uint32_t)(q0 + lane + kRunStep * k), 0, 0) : 1u;
     };
@@ -1715,12 +1451,8 @@ __global__ __launch_bounds__(kCurvNT, kDebug ? 2 : SSF_FEAT_RUN_WAVES) void k_fe
         const float ra = cz * __builtin_amdgcn_rsqf(r2);
         // (no upper bound on r2 needed: r2 = +inf gives ra = 0 = the exact z / sqrtf(inf); the
         // lower one keeps zero and denormal r2 off the fast path)
-#if SSF_FEAT_RUN_BALLOT1
-        const uint64_t INR = __builtin_amdgcn_ballot_w64((ra >= glo) & (ra < ghi) & (r2 > 1e-30f));
-#else
         const uint64_t INR = __builtin_amdgcn_ballot_w64(ra >= glo) & __builtin_amdgcn_ballot_w64(ra < ghi) &
                              __builtin_amdgcn_ballot_w64(r2 > 1e-30f);
-#endif
         if (k >= 1 && k <= kint && INR == ~0ull) {           // uniform: an interior register, all row g
             float dx, dy, dz;
             lane_tap11x3(cx, cy, cz, dx, dy, dz);
@@ -1957,7 +1689,7 @@ __global__ __launch_bounds__(kSelThreads) void k_feat_select(const float* __rest
     __shared__ int lb[kMaxRows + 1];                          // per-row slot bases of the LDS selections
     __shared__ int pre[2][kMaxRows + 1];
     // per chunk: 1 = general-kernel block (positions from the u16 index), else its row -> lane map
-    // (k_feat_chunk_reg: a selected point's chunk position is 64 x its own column + that lane)
+    // (k_feat_wave_reg: a selected point's chunk position is 64 x its own column + that lane)
     __shared__ uint8_t irc[kFeatMaxChunks];
     __shared__ uint8_t lmc[kFeatMaxChunks][kMaxRows];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -2076,11 +1808,6 @@ __global__ __launch_bounds__(kSelThreads) void k_feat_select(const float* __rest
     if (curv_cm)                                              // debug: the row bases for k_feat_debug
         for (int k = tid; k < (ncf + 1) * kMaxRows; k += kSelThreads)
             C[k] = rb[k % kMaxRows][k / kMaxRows];
-#if SSF_SEL_CUT == 1                                          // timing only (tools)
-    __syncthreads();
-    if (tid == 0) plane_count[f] = 0;
-    return;
-#endif
     // candidate planes: every (chunk, row) segment of a row in range to its ring-order bits,
     // one plane at a time through the staging copy
 #pragma unroll
@@ -2117,11 +1844,6 @@ __global__ __launch_bounds__(kSelThreads) void k_feat_select(const float* __rest
             }
         }
     }
-#if SSF_SEL_CUT == 2                                          // timing only (tools)
-    __syncthreads();
-    if (tid == 0) plane_count[f] = 0;
-    return;
-#endif
     // the unresolved own points of rows in range
 #pragma unroll
     for (int i = 0; i < kWPT; ++i) {
@@ -2162,11 +1884,6 @@ __global__ __launch_bounds__(kSelThreads) void k_feat_select(const float* __rest
         }
     }
     __syncthreads();
-#if SSF_SEL_CUT == 3                                          // timing only (tools)
-    __syncthreads();
-    if (tid == 0) plane_count[f] = 0;
-    return;
-#endif
     // the planar selections (indexInRow per slot) stay in LDS when a frame cannot make more than
     // the staging region holds (sum over rows of ceil(n_r / span) <= nf / span + rows)
     const bool sel_lds = lb[n_rows] <= kFeatMaxChunks * kFeatWords * 2;
@@ -2216,10 +1933,6 @@ __global__ __launch_bounds__(kSelThreads) void k_feat_select(const float* __rest
         if (lane == 63) pre[e ? 1 : 0][n_rows] = incl;
     }
     __syncthreads();
-#if SSF_SEL_CUT == 4                                          // timing only (tools)
-    if (tid == 0) plane_count[f] = 0;
-    return;
-#endif
 #pragma unroll
     for (int e = 0; e < (kEdge ? 2 : 1); ++e) {
         const int* P = pre[e];
@@ -2437,12 +2150,7 @@ size_t feat_irr_bytes(int n_frames, int64_t max_pts) {
     return (size_t)std::max<int64_t>(16, ((int64_t)n_frames * nc + 15) & ~(int64_t)15);
 }
 bool feat_single_read(int64_t max_pts) {
-#ifdef SSF_FEAT_LEGACY
-    (void)max_pts;
-    return false;
-#else
     return (max_pts + kBinChunk - 1) / kBinChunk <= kFeatMaxChunks;
-#endif
 }
 
 size_t flag_bytes(int64_t total, int n_frames) { return (size_t)(total + 64 * (int64_t)n_frames + 64); }
@@ -2470,29 +2178,19 @@ hipError_t launch_extract_planes(hipStream_t s, const ssf_config& cfg, int n_fra
         const dim3 grid((unsigned)((nblk + 7) / 8 * 8));
         // unmasked 64-beam frames: the regular-window kernel first, then the general one for the
         // blocks it flagged (every other block returns at once)
-        const bool regular = SSF_FEAT_REGULAR && !keep && R == kMaxRows && fs->irr && fs->lmap &&
+        const bool regular = !keep && R == kMaxRows && fs->irr && fs->lmap &&
                              stride <= 4096;              // k_feat_wave_reg: 32-bit window offsets
         // the run kernel next, for the chunks k_feat_wave_reg left (every chunk when it did not
         // run: masked frames, 16 beams); then k_feat_chunk for the rest
-        const bool run = SSF_FEAT_WAVE_RUN && fs->irr && stride <= 4096;
+        const bool run = fs->irr && stride <= 4096;
         uint8_t* irr = (regular || run) ? fs->irr : nullptr;
         const RingTable* rt = reinterpret_cast<const RingTable*>(fs->rtab);
-        if (regular && SSF_FEAT_WAVE_REG) {                   // one wave per chunk
+        if (regular) {                                        // one wave per chunk
             kmark(s, "k_feat_wave_reg");
             const int64_t nwg = (nblk + kCurvNW - 1) / kCurvNW;
             const dim3 wgrid((unsigned)((nwg + 7) / 8 * 8));
 #define SSF_FR_LAUNCH(D, E)                                                                         \
             hipLaunchKernelGGL((k_feat_wave_reg<D, E>), wgrid, dim3(kCurvNT), 0, s, pts, stride,     \
-                               frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
-                               cfg.plane_min, emin, rt, fs->cnt, fs->gidx, fs->gbits, ccm, irr,    \
-                               fs->lmap)
-            if (edge) { if (dbg) SSF_FR_LAUNCH(true, true); else SSF_FR_LAUNCH(false, true); }
-            else { if (dbg) SSF_FR_LAUNCH(true, false); else SSF_FR_LAUNCH(false, false); }
-#undef SSF_FR_LAUNCH
-        } else if (regular) {
-            kmark(s, "k_feat_chunk_reg");
-#define SSF_FR_LAUNCH(D, E)                                                                         \
-            hipLaunchKernelGGL((k_feat_chunk_reg<D, E>), grid, dim3(kCurvNT), 0, s, pts, stride,     \
                                frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
                                cfg.plane_min, emin, rt, fs->cnt, fs->gidx, fs->gbits, ccm, irr,    \
                                fs->lmap)
@@ -2530,12 +2228,6 @@ hipError_t launch_extract_planes(hipStream_t s, const ssf_config& cfg, int n_fra
 #undef SSF_FC_LAUNCH
         }
 #undef SSF_FC_COMMON
-#if SSF_FEAT_CUT
-        // timing variants (tools only): the chunk kernel stopped early and wrote nothing, so the
-        // select must not read its outputs; empty plane lists instead
-        (void)ring_off; (void)sel;
-        return hipMemsetAsync(plane_count, 0, sizeof(int32_t) * (size_t)n_frames, s);
-#endif
         kmark(s, "k_feat_select");
         if (edge)
             hipLaunchKernelGGL(k_feat_select<true>, dim3(n_frames), dim3(kSelThreads), 0, s, pts, stride,

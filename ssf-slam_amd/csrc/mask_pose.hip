@@ -314,9 +314,6 @@ SSF_DEV void load_raw(const T* __restrict__ P, const T* __restrict__ Fl, int64_t
     r[3] = P[3 * i];  r[4] = P[3 * i + 1];  r[5] = P[3 * i + 2];
 }
 
-#ifndef SSF_EM_OFF32
-#define SSF_EM_OFF32 1                           // EM / Lloyd loads: 32-bit byte offsets from the part's base (A/B: 0)
-#endif
 // three consecutive Ts at byte offset o (< 2^32) of a wave-uniform base: the global_load's SGPR
 // base + 32-bit VGPR offset form, so the clamped index costs a min and a multiply per point
 // instead of 64-bit compares, selects and address arithmetic
@@ -356,163 +353,60 @@ SSF_DEV double uni(double v) {
 // at the join (the record-writing full pass took 411 k cycles against 264 k without records).
 template <int D, class Ts, class Fn>
 SSF_DEV void for_points_deep(const Ts* __restrict__ P, const Ts* __restrict__ Fl, int64_t r0, int64_t r1, Fn&& fn) {
-#if SSF_EM_OFF32
-    {   // frames of at most 2^32 / (3 sizeof(Ts)) points (mask_pose_batch rejects larger ones)
-        if (r1 <= r0) return;                              // uniform (an empty part)
-        const Ts* Pb = P + 3 * r0;
-        const Ts* Fb = Fl + 3 * r0;
-        const uint32_t n = (uint32_t)(r1 - r0), T = blockDim.x, last = n - 1;
-        constexpr uint32_t S = 3 * sizeof(Ts);
-        const uint32_t j0 = threadIdx.x;
-        auto load = [&](uint32_t k, Ts r[6]) { load3_off(Fb, k * S, r); load3_off(Pb, k * S, r + 3); };
-        Ts buf[D][6];
-#pragma unroll
-        for (int d = 0; d < D; ++d) load(min(j0 + d * T, last), buf[d]);
-        for (uint32_t base = j0; base < n; base += D * T) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                const uint32_t j = base + d * T;
-                double x[6];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) x[k] = (double)buf[d][k];
-                load(min(j + D * T, last), buf[d]);
-                fn(r0 + (int64_t)j, x, j < n);
-            }
-        }
-    }
-#else
-    const int64_t T = blockDim.x;
-    const int64_t i0 = r0 + threadIdx.x;
-    if (r1 <= r0) return;                                  // uniform (an empty part)
-    // loads are unconditional (indices clamped to the last point): the compiler can then count
-    // them and wait with vmcnt(N) instead of draining every prefetch at a conditional join
+    // frames of at most 2^32 / (3 sizeof(Ts)) points (mask_pose_batch rejects larger ones)
+    if (r1 <= r0) return;                              // uniform (an empty part)
+    const Ts* Pb = P + 3 * r0;
+    const Ts* Fb = Fl + 3 * r0;
+    const uint32_t n = (uint32_t)(r1 - r0), T = blockDim.x, last = n - 1;
+    constexpr uint32_t S = 3 * sizeof(Ts);
+    const uint32_t j0 = threadIdx.x;
+    auto load = [&](uint32_t k, Ts r[6]) { load3_off(Fb, k * S, r); load3_off(Pb, k * S, r + 3); };
     Ts buf[D][6];
 #pragma unroll
-    for (int d = 0; d < D; ++d) load_raw(P, Fl, min(i0 + d * T, r1 - 1), buf[d]);
-    for (int64_t base = i0; base < r1; base += D * T) {
+    for (int d = 0; d < D; ++d) load(min(j0 + d * T, last), buf[d]);
+    for (uint32_t base = j0; base < n; base += D * T) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            const int64_t i = base + d * T;
+            const uint32_t j = base + d * T;
             double x[6];
 #pragma unroll
             for (int k = 0; k < 6; ++k) x[k] = (double)buf[d][k];
-            load_raw(P, Fl, min(i + D * T, r1 - 1), buf[d]);
-            fn(i, x, i < r1);   // every slot (no branch around the body's stores); val = 0 is weighted out
+            load(min(j + D * T, last), buf[d]);
+            fn(r0 + (int64_t)j, x, j < n);
         }
     }
-#endif
 }
 
 // EM: two points per step (i, i + T) so every parameter read serves both.  The second point of
 // the last step may not exist (w1 = 0: computed on a duplicate, weighted out).  Loads clamped
-// and unconditional, as in for_points.  SSF_EM_DEEP = 1 (default): the next step's pair in
-// registers; 4: staged by LDS-DMA with the parameters in SGPRs, below -- +1.5 % on the mask
-// alone (r6u) but not in the pipeline (r6za / r6zb: its 16 KiB more LDS keeps the other
-// kernels off the mask's CUs; a one-point 2 KiB-slot form without the extra LDS was no faster).
-// Two register pairs in flight, or the loop unrolled with swapping register sets, were 6 % / 4 %
-// slower (the compiler waits for the loads right after issuing them, r6t / r6u).
-#ifndef SSF_EM_DEEP
-#define SSF_EM_DEEP 1
-#endif
-#ifndef SSF_LLOYD_LDS_HOIST
-#define SSF_LLOYD_LDS_HOIST 0                    // Lloyd: the centres' bases laundered once per pass (A/B: 2.3x
-#endif                                           // slower, the centres hoisted into VGPRs spill in the loops, r6zd)
-#ifndef SSF_EM_LDS_HOIST
-#define SSF_EM_LDS_HOIST 1                       // EM: the LDS parameter bases laundered once per pass (r6zc/r6zd)
-#endif
-#ifndef SSF_EM_SGPR
-#define SSF_EM_SGPR (SSF_EM_DEEP == 4)           // E-step parameters as wave-uniform SGPR operands
-#endif
+// and unconditional, as in for_points; the next step's pair is held in registers.  Two register
+// pairs in flight, or the loop unrolled with swapping register sets, were 6 % / 4 % slower (the
+// compiler waits for the loads right after issuing them, r6t / r6u); DESIGN 6.1 lists the other
+// forms that were measured and not kept.
 template <class Ts, class Fn>
 SSF_DEV void for_point_pairs(const Ts* __restrict__ P, const Ts* __restrict__ Fl, int64_t r0, int64_t r1, Fn&& fn) {
-#if SSF_EM_OFF32
-    {   // frames of at most 2^32 / (3 sizeof(Ts)) points (mask_pose_batch rejects larger ones)
-        const Ts* Pb = P + 3 * r0;
-        const Ts* Fb = Fl + 3 * r0;
-        const uint32_t n = (uint32_t)(r1 - r0), T = blockDim.x, last = n - 1;
-        constexpr uint32_t S = 3 * sizeof(Ts);
-        uint32_t i = threadIdx.x;
-        if (i >= n) return;
-        Ts ra[6], rb[6];
-        auto load = [&](uint32_t k, Ts r[6]) { load3_off(Fb, k * S, r); load3_off(Pb, k * S, r + 3); };
-        load(i, ra);
-        load(min(i + T, last), rb);
-        for (; i < n; i += 2 * T) {
-            double xa[6], xb[6];
-#pragma unroll
-            for (int d = 0; d < 6; ++d) { xa[d] = (double)ra[d]; xb[d] = (double)rb[d]; }
-            const double wb = (i + T < n) ? 1.0 : 0.0;
-            load(min(i + 2 * T, last), ra);
-            load(min(i + 3 * T, last), rb);
-            fn(xa, xb, wb);
-        }
-    }
-#else
-    const int64_t T = blockDim.x;
-    int64_t i = r0 + threadIdx.x;
-    if (i >= r1) return;
+    // frames of at most 2^32 / (3 sizeof(Ts)) points (mask_pose_batch rejects larger ones)
+    const Ts* Pb = P + 3 * r0;
+    const Ts* Fb = Fl + 3 * r0;
+    const uint32_t n = (uint32_t)(r1 - r0), T = blockDim.x, last = n - 1;
+    constexpr uint32_t S = 3 * sizeof(Ts);
+    uint32_t i = threadIdx.x;
+    if (i >= n) return;
     Ts ra[6], rb[6];
-    load_raw(P, Fl, i, ra);
-    load_raw(P, Fl, min(i + T, r1 - 1), rb);
-    for (; i < r1; i += 2 * T) {
+    auto load = [&](uint32_t k, Ts r[6]) { load3_off(Fb, k * S, r); load3_off(Pb, k * S, r + 3); };
+    load(i, ra);
+    load(min(i + T, last), rb);
+    for (; i < n; i += 2 * T) {
         double xa[6], xb[6];
 #pragma unroll
         for (int d = 0; d < 6; ++d) { xa[d] = (double)ra[d]; xb[d] = (double)rb[d]; }
-        const double wb = (i + T < r1) ? 1.0 : 0.0;
-        load_raw(P, Fl, min(i + 2 * T, r1 - 1), ra);
-        load_raw(P, Fl, min(i + 3 * T, r1 - 1), rb);
+        const double wb = (i + T < n) ? 1.0 : 0.0;
+        load(min(i + 2 * T, last), ra);
+        load(min(i + 3 * T, last), rb);
         fn(xa, xb, wb);
     }
-#endif
 }
 
-#if SSF_EM_DEEP == 4
-// A/B (SSF_EM_DEEP = 4): the pair of the next step staged by LDS-DMA (global_load_lds_dwordx3: lane l's 12 bytes at
-// base + 16 l, tools/probes/glds_x3_layout.hip) into a per-wave 4 KiB slot (k-means++'s bsum
-// block, idle during EM), so the loads in flight hold no VGPRs and cannot be sunk to their use.
-// Same per-thread point order, so the same sums.  The slot is read (lgkmcnt(0)) before the next
-// DMA overwrites it; vmcnt(0) before the read.  hipcc drains every pending LDS-DMA before any
-// LDS read it cannot prove disjoint, so the loop reads no other LDS: the E-step parameters come
-// in SGPRs (SSF_EM_SGPR).
-SSF_DEV void glds_x3(const float* g, float* lds_base) {
-    __builtin_amdgcn_global_load_lds((const void*)g,
-                                     (__attribute__((address_space(3))) void*)lds_base, 12, 0, 0);
-}
-template <class Fn>
-SSF_DEV void for_point_pairs_glds(const float* __restrict__ P, const float* __restrict__ Fl,
-                                  int64_t r0, int64_t r1, float* slot, Fn&& fn) {
-    const int64_t T = blockDim.x;
-    const int lane = threadIdx.x & 63;
-    int64_t i = r0 + threadIdx.x;
-    if (i >= r1) return;
-    // a lane that has left the loop takes no part in a DMA and its 16 bytes of the slot are not
-    // written (EXEC-masked); the others' land at base + 16 lane as before
-    const int64_t last = r1 - 1;
-    auto issue = [&](int64_t ia, int64_t ib) {
-        ia = min(ia, last); ib = min(ib, last);
-        glds_x3(Fl + 3 * ia, slot);
-        glds_x3(P + 3 * ia, slot + 256);
-        glds_x3(Fl + 3 * ib, slot + 512);
-        glds_x3(P + 3 * ib, slot + 768);
-    };
-    issue(i, i + T);
-    for (; i < r1; i += 2 * T) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): this step's DMA has landed
-        double xa[6], xb[6];
-        const float* s = slot + 4 * lane;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            xa[d] = (double)s[d];       xa[3 + d] = (double)s[256 + d];
-            xb[d] = (double)s[512 + d]; xb[3 + d] = (double)s[768 + d];
-        }
-        __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): the slot is read
-        const double wb = (i + T < r1) ? 1.0 : 0.0;
-        issue(i + 2 * T, i + 3 * T);
-        fn(xa, xb, wb);
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);              // the last (clamped) DMA drained
-}
-#endif
 
 // 1/d for d in [1, 2] (d = 1 + e, e in (0, 1]): v_rcp_f64 and two Newton steps, ~1 ulp,
 // instead of the IEEE division sequence.
@@ -653,11 +547,7 @@ struct Split {
 // guarantee.  So the exchange also carries the architectural pair: an agent-scope release fence
 // before the arrival add and an agent-scope acquire after the poll (round 3).  Cost,
 // same box A/B: configs[1] latency 0.554 -> 0.574 ms, configs[2] as written 4868 -> 4715
-// frames/s (tools/gpu/r3i.sh); B = 256 runs G = 1 and never exchanges.  -DSSF_MASK_XCHG_FENCES=0
-// drops the pair (A/B only).
-#ifndef SSF_MASK_XCHG_FENCES
-#define SSF_MASK_XCHG_FENCES 1
-#endif
+// frames/s (tools/gpu/r3i.sh); B = 256 runs G = 1 and never exchanges.
 
 // lane 0: wait until the frame's arrival counter reaches `target` (relaxed sc1 polls with
 // s_sleep back-off); false when a partner reported a timeout or the spin bound ran out
@@ -690,16 +580,12 @@ SSF_DEV bool exchange(Split& X, double (&v)[N], double* tmp, int* okflag) {
         // barrier that keeps them above the add
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (threadIdx.x == 0) {
-#if SSF_MASK_XCHG_FENCES
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             __hip_atomic_fetch_add(X.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int ok = wait_arrivals(X, (uint32_t)X.G * X.seq) ? 1 : 0;
-#if SSF_MASK_XCHG_FENCES
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             *okflag = ok;
         }
     }
@@ -744,16 +630,12 @@ SSF_DEV bool exchange_prefix(Split& X, double v, double* tmp, int* okflag, doubl
     if (threadIdx.x < 64) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (threadIdx.x == 0) {
-#if SSF_MASK_XCHG_FENCES
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             __hip_atomic_fetch_add(X.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int ok = wait_arrivals(X, (uint32_t)X.G * X.seq) ? 1 : 0;
-#if SSF_MASK_XCHG_FENCES
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             *okflag = ok;
         }
     }
@@ -805,11 +687,7 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
     __shared__ double red[kNW * 32];
     __shared__ int ired[kNW];
     __shared__ unsigned long long cand_lds[2];
-#if SSF_EM_DEEP == 4
-    __shared__ __attribute__((aligned(16))) double bsum[kKppBlocks > kNW * 512 ? kKppBlocks : kNW * 512];  // + the EM's DMA slots
-#else
     __shared__ double bsum[kKppBlocks];   // k-means++ per-64-point-block distance totals
-#endif
     __shared__ uint32_t lq[kNW * kLQ];     // Lloyd skip passes: per-wave relabel entries of a trip
     __shared__ double xtmp[kSlot + kMaxSplit * kSlot];   // exchange totals + the gathered parts
     __shared__ int tk, okflag;
@@ -1224,15 +1102,8 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
         // sums (full pass) or sum deltas (skip pass), changed count, new record
         // (val = 0: a pipeline slot with no point -- computed, weighted out, record written to
         // the frame's spare slot n)
-#if SSF_LLOYD_LDS_HOIST
-        const LdsDouble* cenL = lds_laundered(S.cen);   // once per pass (see SSF_EM_LDS_HOIST)
-#endif
         auto label = [&](auto wrec_c, int64_t i, const double* x, int lp, bool val) {
-#if SSF_LLOYD_LDS_HOIST
-            const LdsDouble* cen = cenL;
-#else
             const LdsDouble* cen = lds_laundered(S.cen);
-#endif
             double v[6], dt0 = 0.0, dt1 = 0.0, vn = 0.0;
 #pragma unroll
             for (int d = 0; d < 6; ++d) {
@@ -1257,16 +1128,9 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
             // every point: a prefetched stream of [flow, xyz]; the previous label is recomputed
             // from the previous centres (the pass that wrote it used the same expression)
             const double cpn0 = uni(S.csnp[0]), cpn1 = uni(S.csnp[1]);
-#if SSF_LLOYD_LDS_HOIST
-            const LdsDouble* cenpL = lds_laundered(S.cenp);
-#endif
             auto full_pass = [&](auto wrec_c) {
                 for_points_deep<kLloydDeep>(P, Fl, r0, r1, [&](int64_t i, const double* x, bool val) {
-#if SSF_LLOYD_LDS_HOIST
-                    const LdsDouble* cenp = cenpL;
-#else
                     const LdsDouble* cenp = lds_laundered(S.cenp);
-#endif
                     double dp0 = 0.0, dp1 = 0.0;
 #pragma unroll
                     for (int d = 0; d < 6; ++d) {
@@ -1311,11 +1175,7 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
                         const int tr = (int)(gy & 0x1FFu);
                         const float nv = __uint_as_float(gy & 0x7FFFFE00u);
                         const bool skip = __uint_as_float(gx) > __builtin_fmaf(S.lb1[tr], nv, S.lb2[tr]) * 1.00001f;
-#ifdef SSF_LLOYD_EXP_NOQUEUE
-                        const bool nd = (i < we) & !skip & (gx == 0x7FFFFFFFu);
-#else
                         const bool nd = (i < we) & !skip;
-#endif
                         const uint64_t m = __ballot(nd);
                         if (nd) Q[nl + __popcll(m & lanemask_lt())] = (uint32_t)i | (gy & 0x80000000u);
                         nl += __popcll(m);
@@ -1479,38 +1339,15 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
         if (it == 1 && tid == 0) S.dg_e[0] = S.dg_e[1] = S.dg_e[2] = 0.0;
         const unsigned long long e_t0 = __builtin_amdgcn_s_memtime();
 #endif
-#if SSF_EM_SGPR
-        // the 27 E-step parameters as wave-uniform SGPR operands, read
-        // from LDS once per pass instead of once per point pair
-        double Aqs[21], bqs[6];
-#pragma unroll
-        for (int k = 0; k < 21; ++k) Aqs[k] = uni(S.Aq[k]);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) bqs[k] = uni(S.bq[k]);
-#elif SSF_EM_LDS_HOIST
         // the laundered LDS bases outside the loop: two loop-invariant VGPRs.  Laundered per
         // pair, their constants were rematerialised every iteration into registers the
         // prefetched point loads had landed in, so the loads were copied away (and waited for)
         // right after they were issued
         const LdsDouble* AqL = lds_laundered(S.Aq);
         const LdsDouble* bqL = lds_laundered(S.bq);
-#endif
-#if SSF_EM_DEEP == 4
-        auto em_pair = [&](const double* xa, const double* xb, double wb) {
-#else
         for_point_pairs(P, Fl, r0, r1, [&](const double* xa, const double* xb, double wb) {
-#endif
-#if SSF_EM_SGPR
-            const double* Aq = Aqs;
-            const double* bq = bqs;
-#elif SSF_EM_LDS_HOIST
             const LdsDouble* Aq = AqL;
             const LdsDouble* bq = bqL;
-#else
-            // Aq / bq are re-read from LDS once per PAIR of points (lds_laundered)
-            const LdsDouble* Aq = lds_laundered(S.Aq);
-            const LdsDouble* bq = lds_laundered(S.bq);
-#endif
             double va[6], vb[6];
 #pragma unroll
             for (int a = 0; a < 6; ++a) { va[a] = xa[a] - mean[a]; vb[a] = xb[a] - mean[a]; }
@@ -1537,15 +1374,7 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
                     for (int b = a; b < 6; ++b) acc[7 + up(a, b)] += rv * v[b];
                 }
             }
-#if SSF_EM_DEEP == 4
-        };
-        if constexpr (sizeof(T) == 4)
-            for_point_pairs_glds(P, Fl, r0, r1, reinterpret_cast<float*>(bsum) + (tid >> 6) * 1024, em_pair);
-        else
-            for_point_pairs(P, Fl, r0, r1, em_pair);
-#else
         });
-#endif
         acc[28] += log(prod) + (double)pexp * 0.69314718055994530942;
         block_sum_rs<29>(acc, red);
 #ifdef SSF_MASK_STAMPS

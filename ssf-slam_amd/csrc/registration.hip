@@ -1,18 +1,35 @@
 // registration.hip -- lidarOdometry_onlyPC::frameRegistration (src/lidarOdometry_onlyPC.cpp:147-252)
 // on gfx950, batched over independent frame pairs.
 //
-//   k_plane_table  per LAST-frame plane point a: exact 30-NN (FLANN L2_Simple float distances,
-//                  ties to the lower index) over the frame's plane cloud streamed through LDS
-//                  tiles, ring-diverse 5-point pick (:180-205), gate d2[n] < 1 (:207), 5x3
-//                  column-pivoted Householder least squares (:208-220), coplanarity gate (:222-232).
-//                  Everything there depends only on (last frame, a), so it is computed once per
-//                  frame here instead of twice per correspondence.
-//   k_associate    per CURRENT plane point: transformToLast in double (:74-82) -> exact 1-NN in the
-//                  last plane cloud (:168, unbounded) -> correspondence record {po, pa, n, valid}.
-//   k_solve        one work-group per pair runs the whole Ceres-LM (or GN) loop on device:
-//                  residual/Jacobian/Huber evaluation in f64 over the records, deterministic
-//                  block reduction of the 28 normal-equation terms, and the 6x6 trust-region
-//                  step on one lane -- no host round trip between iterations.
+// Per LAST-frame plane point a, the plane table: exact 30-NN (FLANN L2_Simple float distances,
+// ties to the lower index), ring-diverse 5-point pick (:180-205), gate d2[n] < 1 (:207), 5x3
+// column-pivoted Householder least squares (:208-220), coplanarity gate (:222-232).  It depends
+// only on (last frame, a), so it is computed once per frame instead of twice per correspondence.
+// Per CURRENT plane point, the association: transformToLast in double (:74-82) -> exact 1-NN in
+// the last plane cloud (:168, unbounded) -> correspondence record {po, pa, n, valid}.  Per pair,
+// the solve.  launch_plane_table / launch_register pick the kernels (register_plan):
+//
+//   k_plane_table_sorted  frames of up to kSortMax plane points: one work-group per frame sorts
+//                         it by x (rocPRIM radix sort), rebuilds it as y-strips in LDS and
+//                         answers every query from a bounded walk over three strips; writes the
+//                         sorted copy and the strip image the association reuses.
+//   k_plane_table         larger frames: brute force over the frame streamed through LDS tiles.
+//   k_associate_strips    last frames of up to kSortMax points: the strip image staged in LDS,
+//                         1-NN by radius doubling over strip rings.  <kSoa, 0>: one query per
+//                         lane (big launches; with one work-group per pair it writes the
+//                         records compacted for the solve); <kSoa, kAssocCoopG>: one query per
+//                         lane group (launches of at most kAssocCoopPairs pairs).  A last frame
+//                         above the staging capacity walks the x-sorted copy in global memory.
+//   k_associate           larger last frames (or no sorted copy): brute force.
+//   k_solve               one work-group per pair runs the whole Ceres-LM or GN loop on device
+//                         (one instantiation per mode): residual / Jacobian / Huber evaluation
+//                         in f64 over the records in LDS, deterministic block reduction of the
+//                         28 normal-equation terms, and the 6x6 step redundantly in every
+//                         thread -- no host round trip and no lane-0 section between iterations.
+//   k_edge_table, k_edge_associate   the point-to-line extension (off by default); its blocks
+//                         join k_solve<true, ..>'s evaluations.
+//   k_strip_invalidate    marks the strip images stale after a k_plane_table launch.
+//   k_accumulate          chains relative poses into absolute ones.
 #include "ssf_device.hpp"
 #include "ssf_internal.hpp"
 
@@ -396,29 +413,12 @@ constexpr int kTableStripSoaMax = 10624;  // ... and up to this size strips of 1
 // Sorted-point views the walks read through (all inlined; the address space of each pointer --
 // LDS or global -- is inferred at the call site):
 //   PtsF4  16-B points (x, y, z, -) + a separate int permutation (sorted rank -> original index)
-//   PtsSoA x / y / z float arrays + a u16 permutation: 14 B per point, so ~9k-point frames fit in
-//          LDS next to the deferred-query grid
 struct PtsF4 {
     const float4* S;
     const int* I;
     SSF_DEV float4 pt(int c) const { return S[c]; }
     SSF_DEV int id(int c) const { return I[c]; }
 };
-struct PtsSoA {
-    const float* X;
-    const float* Y;
-    const float* Z;
-    const uint16_t* I;
-    SSF_DEV float4 pt(int c) const { return make_float4(X[c], Y[c], Z[c], 0.f); }
-    SSF_DEV int id(int c) const { return (int)I[c]; }
-};
-
-struct PtsF4W {                     // 16-B points with the original index in .w
-    const float4* S;
-    SSF_DEV float4 pt(int c) const { return S[c]; }
-    SSF_DEV int id(int c) const { return __float_as_int(S[c].w); }
-};
-
 template <class V>
 SSF_DEV void knn_walk(const V& v, int m, int r, const float4& q, bool bounded, double (&kk)[kK]) {
     const float lim = bounded ? 1.0f : __builtin_inff();
@@ -651,8 +651,7 @@ constexpr int kStripPerMax = kSortMax / kStripThreads;   // x-order points per t
 // r = k kStripThreads + tid with its original index in .w.  Writes the strip-major points (F,
 // or X | Y | Z + I16), T.start / T.ylo / T.yhi; returns the strip geometry.
 template <bool kSoa, int kPer, class Get>
-SSF_DEV StripGeo strips_build(Get get, int m, StripLds& T, float4* F, float* X, uint16_t* I16,
-                              float wmin = 1.001f) {
+SSF_DEV StripGeo strips_build(Get get, int m, StripLds& T, float4* F, float* X, uint16_t* I16) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     float y0 = __builtin_inff(), y1 = -__builtin_inff();
 #pragma unroll
@@ -670,11 +669,10 @@ SSF_DEV StripGeo strips_build(Get get, int m, StripLds& T, float4* F, float* X, 
     y0 = __builtin_inff(); y1 = -__builtin_inff();
     for (int k = 0; k < kStripWaves; ++k) { y0 = fminf(y0, T.red[2 * k]); y1 = fmaxf(y1, T.red[2 * k + 1]); }
     g.y0 = y0;
-    // W > 1 m (wmin) by a margin far above the float error of the strip assignment: a point two
-    // strips away from the query's is then always more than 1 m away (the bounded 30-NN searches
-    // the query's strip and its two neighbours only).  The plane table's pick walks take
-    // wmin = 0.5005 (visit_1m then covers two strips on each side).
-    g.W = fmaxf(wmin, (y1 - y0) / (float)(kStripMax - 1));
+    // W > 1 m by a margin far above the float error of the strip assignment: a point two strips
+    // away from the query's is then always more than 1 m away (the bounded 30-NN and the pick
+    // walks search the query's strip and its two neighbours only)
+    g.W = fmaxf(1.001f, (y1 - y0) / (float)(kStripMax - 1));
     g.invW = 1.0f / g.W;
     g.ns = min(kStripMax, (int)((y1 - y0) * g.invW) + 1);
     // histogram (cursor holds the counts), exclusive scan into start
@@ -814,9 +812,6 @@ constexpr int kDeferRings = SSF_DEFER_RINGS;     // deferred queries: strips wit
 #ifndef SSF_DEFER_FIRST
 #define SSF_DEFER_FIRST 2
 #endif
-#ifndef SSF_DEFER_MID
-#define SSF_DEFER_MID 0
-#endif
 constexpr int kDeferFirst = SSF_DEFER_FIRST;     // ... searched first within this many metres
 
 SSF_DEV void table_deferred_walk(const float4* __restrict__ P, const float4* __restrict__ SP,
@@ -912,14 +907,9 @@ SSF_DEV void strip_visit(const StripView<false>& v, const StripLds& T, int sidx,
     }
 }
 
-// The 1-m region: the query's strip and its neighbours -- one on each side for strips wider
-// than 1 m, two for strips of 0.5 .. 1 m (SSF_TABLE_PICK_W).  pos: the start positions in the
-// query's strip (its own) and the neighbours (-1 until found).
-#ifndef SSF_TABLE_PICK_W
-#define SSF_TABLE_PICK_W 1.001f                  // pick-walk strip width floor (0.5005f: five strips, r5aq: 0.342 vs 0.276 ms, slower)
-#endif
-constexpr float kPickStripW = SSF_TABLE_PICK_W;
-constexpr int kPos1m = kPickStripW < 1.0f ? 5 : 3;
+// The 1-m region: the query's strip and its neighbour on each side (strips are wider than 1 m).
+// pos: the start positions in the query's strip (its own) and the neighbours (-1 until found).
+constexpr int kPos1m = 3;
 template <class Bound, class Body>
 SSF_DEV void visit_1m(const StripView<false>& v, const StripLds& T, const StripGeo& g, int (&pos)[kPos1m],
                       const float4& q, Bound&& bound, Body&& body) {
@@ -927,10 +917,6 @@ SSF_DEV void visit_1m(const StripView<false>& v, const StripLds& T, const StripG
     strip_visit(v, T, s0, pos[0], q, 1.0f, bound, body);
     if (s0 + 1 < g.ns) strip_visit(v, T, s0 + 1, pos[1], q, 1.0f, bound, body);
     if (s0 - 1 >= 0) strip_visit(v, T, s0 - 1, pos[2], q, 1.0f, bound, body);
-    if (kPos1m == 5 && g.W < 1.0f) {                                   // uniform per frame
-        if (s0 + 2 < g.ns) strip_visit(v, T, s0 + 2, pos[kPos1m == 5 ? 3 : 0], q, 1.0f, bound, body);
-        if (s0 - 2 >= 0) strip_visit(v, T, s0 - 2, pos[kPos1m == 5 ? 4 : 0], q, 1.0f, bound, body);
-    }
 }
 
 // Every strip outward from q's, in rings of strips, while a strip can still hold a point with
@@ -1085,10 +1071,7 @@ SSF_DEV bool pick_beyond_invalid(const StripView<false>& v, const StripLds& T, c
     return C < need;
 }
 
-#ifndef SSF_TABLE_COOP_G
-#define SSF_TABLE_COOP_G 4                       // lanes per deferred pick query (0: one lane each)
-#endif
-constexpr int kTableCoopG = SSF_TABLE_COOP_G;
+constexpr int kTableCoopG = 4;                   // lanes per deferred pick query
 // Whole work-group: every query of the frame (m > 30, every ring code < 255).  Queries that need
 // points beyond 1 m (K1 < 30, fewer than two other-ring points inside) are queued and finished
 // afterwards, spread over the waves.
@@ -1137,93 +1120,76 @@ SSF_DEV void table_pick_walks(const float4* __restrict__ P, const StripView<fals
     if (threadIdx.x == 0 && stamp_out) { stamp_out[0] = (int32_t)((__builtin_amdgcn_s_memtime() - stamp0) >> 4); stamp_out[1] = *qlen; }
 #endif
     const int nq = min(*qlen, qcap);
-#if SSF_TABLE_COOP_G
     // one deferred query per group of kTableCoopG lanes: the group's lanes run the 1-m pick
     // redundantly (same bits), then both beyond-1-m searches of pick_beyond_invalid with the
     // strips of each ring round one per lane (strip i of the round order s0, s0+1, s0-1, s0+2,
-    // ...), the group's minimum E / sum C after each round -- a lane alone walked every ring
-    // (the slowest deferred query set the frame's time: ~0.127 M of ~0.60 M cycles, r03 stamps)
-    {
-        constexpr int G = kTableCoopG;
-        const int gl = threadIdx.x % G, ng = blockDim.x / G;
-        for (int k = threadIdx.x / G; k < nq; k += ng) {
-            const int j = queue[k];                                       // uniform per group
-            const float4 q = v.pt(j);
-            const int64_t o = base + v.id(j);
-            PickState s;
-            pick_1m(P, v, T, g, j, q, s);
-            const bool f1 = key_dist(s.d1) < 1.0f;
-            const int prow = s.prow, s0 = g.strip_of(q.y), nstrip = 2 * g.ns;   // round order
-            auto strip_at = [&](int i) { return i == 0 ? s0 : ((i & 1) ? s0 + (i + 1) / 2 : s0 - i / 2); };
-            auto ring_at = [&](int i) { return (i + 1) / 2; };
-            // E: the smallest key of an other-ring point beyond 1 m
-            double E = knn_key(__builtin_inff(), 0x7fffffff);
-            for (int i0 = 0; i0 < nstrip; i0 += G) {
-                // a round's strips all have rings >= ring_at(i0): their |dy| >= (r - 1) W
-                const float lb = (float)(ring_at(i0) - 1) * g.W - 0.001f;
-                if (i0 > 0 && lb > 0.0f && lb * lb > key_dist(E)) break;   // uniform per group
-                const int i = i0 + gl, sidx = strip_at(i);
-                if (i < nstrip && sidx >= 0 && sidx < g.ns) {
-                    int st = sidx == s0 ? j : -1;
-                    strip_visit(v, T, sidx, st, q, __builtin_inff(), [&] { return key_dist(E); },
-                                [&](const float4& p) {
-                                    const float d = l2_simple(q, p);
-                                    const int row = pt_row(p);
-                                    const double key = pick_key(d, p);
-                                    if (d >= 1.0f && row != prow && row <= 63 && key < E) E = key;
-                                });
-                }
-#pragma unroll
-                for (int x = G / 2; x >= 1; x >>= 1) {
-                    const double y = __shfl_xor(E, x, kWave);
-                    E = y < E ? y : E;
-                }
-            }
-            bool inval = false;
-            if (key_dist(E) < __builtin_inff()) {
-                // C: keys beyond 1 m below E; invalid iff C < 30 - K1
-                const int need = 30 - s.K1;
-                const float lim = key_dist(E);
-                int C = 0;
-                for (int i0 = 0; i0 < nstrip; i0 += G) {
-                    const float lb = (float)(ring_at(i0) - 1) * g.W - 0.001f;
-                    if (C >= need || (i0 > 0 && lb > 0.0f && lb * lb > lim)) break;   // uniform per group
-                    const int i = i0 + gl, sidx = strip_at(i);
-                    int c = 0;
-                    if (i < nstrip && sidx >= 0 && sidx < g.ns) {
-                        int st = sidx == s0 ? j : -1;
-                        strip_visit(v, T, sidx, st, q, __builtin_inff(), [&] { return lim; },
-                                    [&](const float4& p) {
-                                        const float d = l2_simple(q, p);
-                                        c += (d >= 1.0f && pick_key(d, p) < E);
-                                    });
-                    }
-#pragma unroll
-                    for (int x = G / 2; x >= 1; x >>= 1) c += __shfl_xor(c, x, kWave);
-                    C += c;
-                }
-                inval = C < need;
-            }
-            if (gl == 0) {
-                if (inval) pick_invalid(o, normal, valid);
-                else pick_finish(P, s, f1 ? 1 : 0, plane_max, o, normal, valid);
-            }
-        }
-    }
-#else
-    const int nw = blockDim.x >> 6, t2 = (threadIdx.x & 63) * nw + (threadIdx.x >> 6);
-    for (int k = t2; k < nq; k += blockDim.x) {
-        const int j = queue[k];
+    // ...), the group's minimum E / sum C after each round -- a lane alone would walk every ring
+    // (the slowest deferred query then sets the frame's time: ~0.127 M of ~0.60 M cycles, r03 stamps)
+    constexpr int G = kTableCoopG;
+    const int gl = threadIdx.x % G, ng = blockDim.x / G;
+    for (int k = threadIdx.x / G; k < nq; k += ng) {
+        const int j = queue[k];                                       // uniform per group
         const float4 q = v.pt(j);
         const int64_t o = base + v.id(j);
         PickState s;
         pick_1m(P, v, T, g, j, q, s);
         const bool f1 = key_dist(s.d1) < 1.0f;
-        const bool inval = pick_beyond_invalid(v, T, g, j, q, s);
-        if (inval) pick_invalid(o, normal, valid);
-        else pick_finish(P, s, f1 ? 1 : 0, plane_max, o, normal, valid);
+        const int prow = s.prow, s0 = g.strip_of(q.y), nstrip = 2 * g.ns;   // round order
+        auto strip_at = [&](int i) { return i == 0 ? s0 : ((i & 1) ? s0 + (i + 1) / 2 : s0 - i / 2); };
+        auto ring_at = [&](int i) { return (i + 1) / 2; };
+        // E: the smallest key of an other-ring point beyond 1 m
+        double E = knn_key(__builtin_inff(), 0x7fffffff);
+        for (int i0 = 0; i0 < nstrip; i0 += G) {
+            // a round's strips all have rings >= ring_at(i0): their |dy| >= (r - 1) W
+            const float lb = (float)(ring_at(i0) - 1) * g.W - 0.001f;
+            if (i0 > 0 && lb > 0.0f && lb * lb > key_dist(E)) break;   // uniform per group
+            const int i = i0 + gl, sidx = strip_at(i);
+            if (i < nstrip && sidx >= 0 && sidx < g.ns) {
+                int st = sidx == s0 ? j : -1;
+                strip_visit(v, T, sidx, st, q, __builtin_inff(), [&] { return key_dist(E); },
+                            [&](const float4& p) {
+                                const float d = l2_simple(q, p);
+                                const int row = pt_row(p);
+                                const double key = pick_key(d, p);
+                                if (d >= 1.0f && row != prow && row <= 63 && key < E) E = key;
+                            });
+            }
+#pragma unroll
+            for (int x = G / 2; x >= 1; x >>= 1) {
+                const double y = __shfl_xor(E, x, kWave);
+                E = y < E ? y : E;
+            }
+        }
+        bool inval = false;
+        if (key_dist(E) < __builtin_inff()) {
+            // C: keys beyond 1 m below E; invalid iff C < 30 - K1
+            const int need = 30 - s.K1;
+            const float lim = key_dist(E);
+            int C = 0;
+            for (int i0 = 0; i0 < nstrip; i0 += G) {
+                const float lb = (float)(ring_at(i0) - 1) * g.W - 0.001f;
+                if (C >= need || (i0 > 0 && lb > 0.0f && lb * lb > lim)) break;   // uniform per group
+                const int i = i0 + gl, sidx = strip_at(i);
+                int c = 0;
+                if (i < nstrip && sidx >= 0 && sidx < g.ns) {
+                    int st = sidx == s0 ? j : -1;
+                    strip_visit(v, T, sidx, st, q, __builtin_inff(), [&] { return lim; },
+                                [&](const float4& p) {
+                                    const float d = l2_simple(q, p);
+                                    c += (d >= 1.0f && pick_key(d, p) < E);
+                                });
+                }
+#pragma unroll
+                for (int x = G / 2; x >= 1; x >>= 1) c += __shfl_xor(c, x, kWave);
+                C += c;
+            }
+            inval = C < need;
+        }
+        if (gl == 0) {
+            if (inval) pick_invalid(o, normal, valid);
+            else pick_finish(P, s, f1 ? 1 : 0, plane_max, o, normal, valid);
+        }
     }
-#endif
 #ifdef SSF_TABLE_STAMPS
     __syncthreads();
     if (threadIdx.x == 0 && stamp_out) stamp_out[4] = (int32_t)((__builtin_amdgcn_s_memtime() - stamp0) >> 4);
@@ -1275,12 +1241,6 @@ SSF_DEV void table_strip_walks(const float4* __restrict__ P, const StripView<kSo
         // part of the list settles it (deferred_decides); else the x-sorted global copy, unbounded
         strip_knn_radius<kDeferFirst>(v, T, g, j, q, kk);
         int dec = deferred_decides(P, kk, (float)(kDeferFirst * kDeferFirst));
-#if SSF_DEFER_MID
-        if (dec == 0) {
-            strip_knn_radius<SSF_DEFER_MID>(v, T, g, j, q, kk);
-            dec = deferred_decides(P, kk, (float)(SSF_DEFER_MID * SSF_DEFER_MID));
-        }
-#endif
         if (dec == 0) {
             strip_knn_radius<kDeferRings>(v, T, g, j, q, kk);
             dec = deferred_decides(P, kk, (float)(kDeferRings * kDeferRings));
@@ -1368,7 +1328,6 @@ SSF_DEV void table_sort_regs(const float4* __restrict__ P, int m, float* key, in
 // block_radix_sort, keys and the index in registers, E per thread in blocked order, so equal
 // keys keep index order): x + 0 turns -0 into +0 (lex_less compares them equal), the sign-flip
 // encoding orders the floats as unsigned words, and slots past m take the largest key.
-// -DSSF_TABLE_BITONIC restores the bitonic network (A/B).
 template <int E>
 SSF_DEV void table_sort_radix(const float4* __restrict__ P, int m, void* storage, int* idx) {
     using Sort = rocprim::block_radix_sort<unsigned int, kTableThreads, E, int>;
@@ -1418,18 +1377,11 @@ __global__ __launch_bounds__(kTableThreads) void k_plane_table_sorted(
 #endif
     int np = 1;
     while (np < m) np <<= 1;
-#ifndef SSF_TABLE_BITONIC
     // the key region [0, 64 KiB) holds the radix sort's storage (the keys stay in registers)
     if (np <= kTableThreads) table_sort_radix<1>(P, m, lds, idx);
     else if (np == 2 * kTableThreads) table_sort_radix<2>(P, m, lds, idx);
     else if (np == 4 * kTableThreads) table_sort_radix<4>(P, m, lds, idx);
     else if (np == 8 * kTableThreads) table_sort_radix<8>(P, m, lds, idx);
-    else
-#endif
-    if (np == 4 * kTableThreads) table_sort_regs<4>(P, m, key, idx);
-    else if (np == 2 * kTableThreads) table_sort_regs<2>(P, m, key, idx);
-    else if (np == kTableThreads) table_sort_regs<1>(P, m, key, idx);
-    else if (np == 8 * kTableThreads) table_sort_regs<8>(P, m, key, idx);
     else if (np == 16 * kTableThreads) table_sort_regs<16>(P, m, key, idx);
     else {
     for (int r = tid; r < np; r += blockDim.x) {
@@ -1530,10 +1482,8 @@ __global__ __launch_bounds__(kTableThreads) void k_plane_table_sorted(
                 p.w = __int_as_float(own[k] | (int)(row_code(p.w) << 16));
                 return p;
             };
-            // the pick walks (rows_ok, m > kK) take the narrower strips; table_strip_walks' ring
-            // searches (strip_knn_radius) count rings in metres and need W > 1 m
-            const StripGeo g = strips_build<false, kStripPerMax>(getp, m, T, F, X, I16,
-                                                                 (rows_ok && m > kK) ? kPickStripW : 1.001f);
+            const bool pick = rows_ok && m > kK;                            // uniform
+            const StripGeo g = strips_build<false, kStripPerMax>(getp, m, T, F, X, I16);
             SSF_TSTAMP_BUILD();
             // results staged in LDS at their original index and stored coalesced at the end when
             // 13 B per point fit behind the strip image with a queue of m / 4 entries (m <= ~5000):
@@ -1541,7 +1491,7 @@ __global__ __launch_bounds__(kTableThreads) void k_plane_table_sorted(
             const int soff = ((int)sizeof(lds) - 16 - 13 * m) & ~15;
             // (one work-group per frame only: a share's results are scattered over the frame)
             const bool stage = nshare == 1 && (soff - qoff) / 4 >= m / 4 + 64;   // uniform
-            if (rows_ok && m > kK && stage) {
+            if (pick && stage) {
                 float* nl = reinterpret_cast<float*>(lds + soff);
                 uint8_t* vl = reinterpret_cast<uint8_t*>(lds + soff + 12 * m);
                 table_pick_walks(P, StripView<false>{F, X, I16, m}, T, g, m, plane_max, 0, nl, vl,
@@ -1551,7 +1501,7 @@ __global__ __launch_bounds__(kTableThreads) void k_plane_table_sorted(
                 uint8_t* gv = valid + base;
                 for (int k = tid; k < 3 * m; k += kTableThreads) gn[k] = nl[k];
                 for (int k = tid; k < m; k += kTableThreads) gv[k] = vl[k];
-            } else if (rows_ok && m > kK)
+            } else if (pick)
                 table_pick_walks(P, StripView<false>{F, X, I16, m}, T, g, m, plane_max, base, normal, valid,
                                  queue, qcap, qlen, stamp_out, st0, share, nshare);
             else
@@ -1570,87 +1520,7 @@ __global__ __launch_bounds__(kTableThreads) void k_plane_table_sorted(
     }
 }
 
-// Association against an x-sorted last frame: binary search of the query's x, then the same
-// outward walk with a 1-element list (ties to the lower original index, as the brute force).
-__global__ __launch_bounds__(256) void k_associate_sorted(
-    const float4* __restrict__ last, const int64_t* __restrict__ last_off,
-    const int32_t* __restrict__ last_count, const float* __restrict__ last_normal,
-    const uint8_t* __restrict__ last_valid, const float4* __restrict__ last_sorted,
-    const int32_t* __restrict__ last_sidx, const float4* __restrict__ curr,
-    const int64_t* __restrict__ curr_off, const int32_t* __restrict__ curr_count,
-    const double* __restrict__ pose_rel, CorrRec* __restrict__ corr, int32_t* __restrict__ nn_out) {
-    const int p = blockIdx.y;
-    const int mc = curr_count[p], ml = last_count[p];
-    if ((int)(blockIdx.x * blockDim.x) >= mc || ml <= 10) return;    // uniform (:158)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= mc) return;
-    const int64_t lo = last_off[p], co = curr_off[p];
-    const float4* SL = last_sorted + lo;
-    const int32_t* SI = last_sidx + lo;
-    const double q[4] = {pose_rel[7 * p], pose_rel[7 * p + 1], pose_rel[7 * p + 2], pose_rel[7 * p + 3]};
-    const double t[3] = {pose_rel[7 * p + 4], pose_rel[7 * p + 5], pose_rel[7 * p + 6]};
-    const float4 pc = curr[co + i];
-    float4 qs;
-    {
-        const double v[3] = {(double)pc.x, (double)pc.y, (double)pc.z};
-        double r[3];
-        quat_rotate(q, v, r);                                          // :74-82
-        qs.x = (float)(r[0] + t[0]); qs.y = (float)(r[1] + t[1]); qs.z = (float)(r[2] + t[2]); qs.w = 0.f;
-    }
-    int lo_i = 0, hi_i = ml;                                            // first x >= qs.x
-    while (lo_i < hi_i) {
-        const int mid = (lo_i + hi_i) >> 1;
-        if (SL[mid].x < qs.x) lo_i = mid + 1; else hi_i = mid;
-    }
-    float best = __builtin_inff();
-    int bi = 0x7fffffff;
-    for (int c = lo_i; c < ml; ++c) {
-        const float4 pl = SL[c];
-        const float dx = qs.x - pl.x;
-        if (dx * dx > best) break;
-        const float d = l2_simple(qs, pl);
-        const int id = SI[c];
-        if (lex_less(d, id, best, bi)) { best = d; bi = id; }
-    }
-    for (int c = lo_i - 1; c >= 0; --c) {
-        const float4 pl = SL[c];
-        const float dx = qs.x - pl.x;
-        if (dx * dx > best) break;
-        const float d = l2_simple(qs, pl);
-        const int id = SI[c];
-        if (lex_less(d, id, best, bi)) { best = d; bi = id; }
-    }
-    const float4* L = last + lo;
-    CorrRec rec;
-    const bool ok = last_valid[lo + bi] != 0;
-    const float4 pa = L[bi];
-    rec.po[0] = pc.x; rec.po[1] = pc.y; rec.po[2] = pc.z; rec.valid = ok ? 1.0f : 0.0f;
-    rec.pa[0] = pa.x; rec.pa[1] = pa.y; rec.pa[2] = pa.z; rec.pad0 = 0.f;
-    const float* nr = last_normal + 3 * (lo + bi);
-    rec.n[0] = nr[0]; rec.n[1] = nr[1]; rec.n[2] = nr[2]; rec.pad1 = 0.f;
-    corr[co + i] = rec;
-    if (nn_out) nn_out[co + i] = bi;
-}
-
-// Same association with the last frame's sorted cloud staged in LDS (x, y, z, original index
-// in .w: 16 B per point, dynamic LDS sized by the launch's plane-point bound).  Each
-// work-group handles kAssocQ queries of one pair in two phases:
-//   1. every query walks outward in x only while dx^2 < R^2 (and dx^2 <= best), R = 1 m.  If
-//      the best squared distance found is < R^2 the answer is exact: any closer point has
-//      dx^2 < R^2 and was visited.  About 95 % of queries finish here.
-//   2. the rest (no point within R: sparse, far regions, where an x-band walk would cover
-//      most of the frame) were queued in LDS; after a barrier they are answered 64 at a time by
-//      an exhaustive scan split over all waves (disjoint slices, merged in LDS).
-// Candidates are compared as (distance, original index), so visit order never changes the result.
-constexpr int kAssocThreads = 1024;
-constexpr int kAssocQ = 2048;              // queries per work-group (2 per thread)
-constexpr int kAssocLdsMax = 6144;         // last-frame plane points staged in LDS (96 KiB)
-constexpr int kAssocSoaMax = 12032;        // ... as 12-B SoA points: 141 KiB + queue + reductions
-#ifndef SSF_ASSOC_BAND2
-#define SSF_ASSOC_BAND2 1.0f
-#endif
-constexpr float kAssocBand2 = SSF_ASSOC_BAND2;   // phase-1 band: dx^2 < 1 (R = 1 m; 0.5 / 0.7 m measured slower)
-
+// The current point in the last frame's coordinates (transformToLast, f64 rotation).
 SSF_DEV float4 assoc_query_point(const float4& pc, const double q[4], const double t[3]) {
     const double v[3] = {(double)pc.x, (double)pc.y, (double)pc.z};
     double r[3];
@@ -1668,8 +1538,7 @@ SSF_DEV bool assoc_better(const V& v, int c, float d, float best, int bc) {
 }
 
 template <class V>
-SSF_DEV void assoc_walk(const V& v, int ml, const float4& qs, float lim, float& best, int& bc,
-                        int* visited = nullptr) {
+SSF_DEV void assoc_walk(const V& v, int ml, const float4& qs, float lim, float& best, int& bc) {
     int lo_i = 0, hi_i = ml;                                            // first x >= qs.x
     while (lo_i < hi_i) {
         const int mid = (lo_i + hi_i) >> 1;
@@ -1693,7 +1562,6 @@ SSF_DEV void assoc_walk(const V& v, int ml, const float4& qs, float lim, float& 
         const float d = l2_simple(qs, pl);
         if (assoc_better(v, c2, d, best, bc)) { best = d; bc = c2; }
     }
-    if (visited) *visited = (c - lo_i) + (lo_i - 1 - c2);
 }
 
 SSF_DEV void assoc_finish(const float4* __restrict__ L, int64_t lo, const float* __restrict__ last_normal,
@@ -1708,164 +1576,6 @@ SSF_DEV void assoc_finish(const float4* __restrict__ L, int64_t lo, const float*
     rec.n[0] = nr[0]; rec.n[1] = nr[1]; rec.n[2] = nr[2]; rec.pad1 = 0.f;
     corr[ci] = rec;
     if (nn_out) nn_out[ci] = bi;
-}
-
-// phases 1 and 2 for one work-group over the sorted last frame v
-template <class V>
-SSF_DEV void assoc_phases(const V& v, int ml, int mc, int i0, int64_t lo, int64_t co,
-                          const double* __restrict__ pose_rel, int p, const float4* __restrict__ curr,
-                          const float4* __restrict__ L, const float* __restrict__ last_normal,
-                          const uint8_t* __restrict__ last_valid, CorrRec* __restrict__ corr,
-                          int32_t* __restrict__ nn_out, int* queue, int* qlen, float* red_d,
-                          int* red_i, unsigned long long* stamp1) {
-    const double q[4] = {pose_rel[7 * p], pose_rel[7 * p + 1], pose_rel[7 * p + 2], pose_rel[7 * p + 3]};
-    const double t[3] = {pose_rel[7 * p + 4], pose_rel[7 * p + 5], pose_rel[7 * p + 6]};
-    const int i1 = min(mc, i0 + kAssocQ);
-    for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {           // phase 1: the x band
-        const float4 pc = curr[co + i];
-        const float4 qs = assoc_query_point(pc, q, t);
-        float best = __builtin_inff();
-        int bc = -1;
-#ifdef SSF_ASSOC_COUNT
-        // diagnostic build only: candidates visited by the phase-1 walk into nn_out
-        // (negative: the query went on to phase 2)
-        int vis = 0;
-        assoc_walk(v, ml, qs, kAssocBand2, best, bc, &vis);
-#else
-        assoc_walk(v, ml, qs, kAssocBand2, best, bc);
-#endif
-        if (best < kAssocBand2) assoc_finish(L, lo, last_normal, last_valid, pc, v.id(bc), corr, nn_out, co + i);
-        else queue[atomicAdd(qlen, 1)] = i;                             // <= kAssocQ entries
-#ifdef SSF_ASSOC_COUNT
-        if (nn_out) nn_out[co + i] = best < kAssocBand2 ? vis : -1 - vis;
-#endif
-    }
-    __syncthreads();
-#ifdef SSF_ASSOC_STAMPS
-    *stamp1 = __builtin_amdgcn_s_memtime();
-#endif
-    // phase 2: the queued queries in groups of 64 (one per lane); for each group all waves scan
-    // disjoint slices of the last frame (broadcast LDS reads, 8 in flight, no divergence) and the
-    // per-slice (distance, rank) bests are merged in LDS -- ties by original index, so exact
-    const int nq = *qlen;
-    const int nw = blockDim.x >> 6, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int chunk = (ml + nw - 1) / nw;
-    const int c0 = min(ml, w * chunk), c1 = min(ml, c0 + chunk);
-    for (int g0 = 0; g0 < nq; g0 += 64) {
-        const int k = g0 + lane;
-        const bool act = k < nq;
-        const int i = queue[act ? k : g0];
-        const float4 pc = curr[co + i];
-        const float4 qs = assoc_query_point(pc, q, t);
-        float best = __builtin_inff();
-        int bc = -1;
-        int c = c0;
-        for (; c + 8 <= c1; c += 8) {
-            float4 pl[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) pl[u] = v.pt(c + u);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float d = l2_simple(qs, pl[u]);
-                if (assoc_better(v, c + u, d, best, bc)) { best = d; bc = c + u; }
-            }
-        }
-        for (; c < c1; ++c) {
-            const float d = l2_simple(qs, v.pt(c));
-            if (assoc_better(v, c, d, best, bc)) { best = d; bc = c; }
-        }
-        red_d[w * 64 + lane] = best;
-        red_i[w * 64 + lane] = bc;
-        __syncthreads();
-        if (w == 0 && act) {
-            for (int u = 1; u < nw; ++u) {
-                const float d = red_d[u * 64 + lane];
-                const int cu = red_i[u * 64 + lane];
-                if (cu >= 0 && assoc_better(v, cu, d, best, bc)) { best = d; bc = cu; }
-            }
-#ifdef SSF_ASSOC_COUNT
-            assoc_finish(L, lo, last_normal, last_valid, pc, v.id(max(bc, 0)), corr, nullptr, co + i);
-#else
-            assoc_finish(L, lo, last_normal, last_valid, pc, v.id(max(bc, 0)), corr, nn_out, co + i);
-#endif
-        }
-        __syncthreads();
-    }
-}
-
-// kSoa = false: the last frame staged as 16-B points (index in .w), up to kAssocLdsMax;
-// kSoa = true:  as x | y | z float arrays (12 B per point, up to kAssocSoaMax), the original index
-//               read from the global permutation on distance ties and for the answer.
-template <bool kSoa>
-__global__ __launch_bounds__(kAssocThreads) void k_associate_lds(
-    const float4* __restrict__ last, const int64_t* __restrict__ last_off,
-    const int32_t* __restrict__ last_count, const float* __restrict__ last_normal,
-    const uint8_t* __restrict__ last_valid, const float4* __restrict__ last_sorted,
-    const int32_t* __restrict__ last_sidx, const float4* __restrict__ curr,
-    const int64_t* __restrict__ curr_off, const int32_t* __restrict__ curr_count,
-    const double* __restrict__ pose_rel, CorrRec* __restrict__ corr, int32_t* __restrict__ nn_out,
-    int lds_cap) {
-    extern __shared__ float4 SLl[];                 // [lds_cap] points, then the queue
-    float* SX = reinterpret_cast<float*>(SLl);
-    int* queue = kSoa ? reinterpret_cast<int*>(SX + 3 * lds_cap) : reinterpret_cast<int*>(SLl + lds_cap);
-    __shared__ int qlen;
-    __shared__ float red_d[kAssocThreads];          // phase-2 per-slice bests
-    __shared__ int red_i[kAssocThreads];
-    const int p = blockIdx.y;
-    const int mc = curr_count[p], ml = last_count[p];
-    const int i0 = blockIdx.x * kAssocQ;
-    if (i0 >= mc || ml <= 10) return;                                   // uniform (:158)
-    const int64_t lo = last_off[p], co = curr_off[p];
-    unsigned long long st1 = 0;
-#ifdef SSF_ASSOC_STAMPS
-    // diagnostic build only: work-group lifetime (s_memtime) into nn_out[co + i0 .. +3]
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-#endif
-    if (threadIdx.x == 0) qlen = 0;
-    const float4* L = last + lo;
-    if (ml <= lds_cap) {
-        if (kSoa) {
-            for (int r = threadIdx.x; r < ml; r += blockDim.x) {
-                const float4 v = last_sorted[lo + r];
-                SX[r] = v.x; SX[ml + r] = v.y; SX[2 * ml + r] = v.z;
-            }
-            __syncthreads();
-            const PtsSoA v{SX, SX + ml, SX + 2 * ml, nullptr};
-            struct View {
-                PtsSoA s;
-                const int32_t* I;
-                SSF_DEV float4 pt(int c) const { return s.pt(c); }
-                SSF_DEV int id(int c) const { return I[c]; }
-            };
-            assoc_phases(View{v, last_sidx + lo}, ml, mc, i0, lo, co, pose_rel, p, curr, L,
-                         last_normal, last_valid, corr, nn_out, queue, &qlen, red_d, red_i, &st1);
-        } else {
-            for (int r = threadIdx.x; r < ml; r += blockDim.x) {
-                float4 v = last_sorted[lo + r];
-                v.w = __int_as_float(last_sidx[lo + r]);
-                SLl[r] = v;
-            }
-            __syncthreads();
-            assoc_phases(PtsF4W{SLl}, ml, mc, i0, lo, co, pose_rel, p, curr, L, last_normal,
-                         last_valid, corr, nn_out, queue, &qlen, red_d, red_i, &st1);
-        }
-    } else {  // a last frame above the caller's plane-point bound (the LDS size): global memory
-        __syncthreads();
-        assoc_phases(PtsF4{last_sorted + lo, last_sidx + lo}, ml, mc, i0, lo, co, pose_rel, p, curr,
-                     L, last_normal, last_valid, corr, nn_out, queue, &qlen, red_d, red_i, &st1);
-    }
-#ifdef SSF_ASSOC_STAMPS
-    __syncthreads();
-    if (threadIdx.x == 0 && nn_out) {
-        const unsigned long long st2 = __builtin_amdgcn_s_memtime();
-        nn_out[co + i0] = qlen;
-        nn_out[co + i0 + 1] = (int32_t)((st1 - st0) >> 4);
-        nn_out[co + i0 + 2] = (int32_t)((st2 - st0) >> 4);
-        nn_out[co + i0 + 3] = qlen;
-    }
-#else
-    (void)st1;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1884,24 +1594,6 @@ __global__ __launch_bounds__(kAssocThreads) void k_associate_lds(
 // kSoa: the strip-major points as x | y | z float arrays and a u16 original index (configs[4]
 // frames); otherwise float4 with the index in .w.  A last frame above the launch's staging
 // capacity walks the x-sorted copy in global memory, unbounded (exact, slow, not expected).
-#ifndef SSF_ASSOC_COMPACT
-#define SSF_ASSOC_COMPACT 1                      // lane-mode association writes compacted records (A/B: 0)
-#endif
-#ifndef SSF_ASSOC_DEFER
-#define SSF_ASSOC_DEFER 0                        // 1: far queries of the lane mode to a wave each (r5u: 256-pair launch 0.135 -> 0.200 ms)
-#endif
-#ifndef SSF_ASSOC_DEFER_R
-#define SSF_ASSOC_DEFER_R 4.0f
-#endif
-constexpr int kAssocDeferMax = 512;              // deferred queries per work-group (more: the lane goes on)
-constexpr float kAssocDeferR = SSF_ASSOC_DEFER_R; // a query still open after this level is deferred
-#ifndef SSF_ASSOC_DEFER_G
-#define SSF_ASSOC_DEFER_G 64
-#endif
-constexpr int kAssocDeferG = SSF_ASSOC_DEFER_G;  // lanes per deferred query (a wave at 64)
-#ifndef SSF_ASSOC_DEFER_EMPTY
-#define SSF_ASSOC_DEFER_EMPTY 0                  // defer only queries with no candidate yet (empty regions)
-#endif
 // kCoopG > 0 (launches of few pairs: a node's one pair, configs[2]'s chained pairs): one query
 // per group of kCoopG lanes instead of one per lane -- the query's strips of each search level
 // spread over the group's lanes (one strip per lane), so no lane walks ring after ring alone,
@@ -1914,10 +1606,6 @@ constexpr int kAssocDeferG = SSF_ASSOC_DEFER_G;  // lanes per deferred query (a 
 #endif
 constexpr int kAssocCoopG = SSF_ASSOC_COOP_G;
 constexpr int kAssocCoopPairs = 16;             // launches of at most this many pairs take the group mode
-#ifndef SSF_ASSOC_BIG_G
-#define SSF_ASSOC_BIG_G 0                        // A/B: group mode with this many lanes for big launches too
-#endif
-constexpr int kAssocBigG = SSF_ASSOC_BIG_G;
 template <bool kSoa, int kCoopG = 0>
 __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
     const float4* __restrict__ last, const int64_t* __restrict__ last_off,
@@ -1935,22 +1623,8 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
     // records (a pair whose records are not compacted gets -1): k_solve then streams them into its
     // LDS with no ballot pass and evaluates them on the way in.  Each query's (1-NN index, valid)
     // goes to nnv first; the ranks need every query's validity.
-    const bool compact = kCoopG == 0 && !SSF_ASSOC_DEFER && ncompact && gridDim.y == 1;   // uniform
+    const bool compact = kCoopG == 0 && ncompact && gridDim.y == 1;   // uniform
     __shared__ int cwave[kStripWaves];
-#if SSF_ASSOC_DEFER == 2
-    // far queries kept by their own wave (no barrier): each wave answers its list in groups of
-    // kAssocDeferG lanes after its lane walks (not in the SoA launch: no LDS left there)
-    constexpr int kDqW = 32;
-    __shared__ int dqw[kSoa ? 1 : kStripWaves][kSoa ? 1 : kDqW];
-    __shared__ int dqnw[kSoa ? 1 : kStripWaves];
-    if (!kSoa && (threadIdx.x & 63) == 0) dqnw[threadIdx.x >> 6] = 0;
-#elif SSF_ASSOC_DEFER
-    // far queries, answered a wave each at the end (the SoA launch has ~0.3 KiB of LDS left)
-    constexpr int kDq = kSoa ? kAssocDeferMax / 4 : kAssocDeferMax;
-    __shared__ int dq[kDq];
-    __shared__ int dqn;
-    if (threadIdx.x == 0) dqn = 0;                  // (the staging's barriers order it)
-#endif
     // gridDim.y work-groups per pair (few pairs in a launch): each stages the whole last frame
     // and answers every gridDim.y-th block of kStripThreads queries
     const int p = blockIdx.x, tid = threadIdx.x;
@@ -2001,7 +1675,7 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
     const StripView<kSoa> v{SL, SX, SI16, ml};
 #ifdef SSF_STRIPS_STAMPS
     rt1 = __builtin_amdgcn_s_memrealtime(); mt1 = __builtin_amdgcn_s_memtime();
-#elif !SSF_ASSOC_DEFER
+#else
     if (kCoopG == 0 && q0 >= mc && !compact) return;                    // (after the barriers of the build)
 #endif
 #ifdef SSF_ASSOC_COUNT
@@ -2055,7 +1729,7 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
     };
     if (kCoopG > 0) {
         // one query per kCoopG-lane group (groups are aligned lane ranges: the reductions stay
-        // inside one), the same levels and bounds as the deferred pass below
+        // inside one), the same levels and bounds as the lane mode below
         const int gl = tid % kCoopG;
         for (int i = (int)blockIdx.y * kQpw + tid / kCoopG; i < mc; i += (int)gridDim.y * kQpw) {   // uniform per group
             const float4 pc = curr[co + i];
@@ -2107,7 +1781,6 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
         // hole, BASELINE configs[2]) therefore walks the points within ~2x its 1-NN distance,
         // not every point within the distance of the first point its own strip happens to hold.
         const int s0 = strip_of(qs.y);
-        bool deferred = false;
         for (float R = 2.0f;; R *= 2.0f) {
             const bool unbounded = R > 4096.0f;                          // uniform per lane
             const float lim = unbounded ? __builtin_inff() : R * R;
@@ -2130,34 +1803,17 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
                 }
             }
             if (best <= lim || unbounded) break;
-#if SSF_ASSOC_DEFER
-            // a far 1-NN: the next levels' ~4 R / W strip searches in a row on one lane set the
-            // wave's (and often the launch's) time -- hand the query to the work-group's queue,
-            // answered below by a whole wave, one strip per lane
-            if (R >= kAssocDeferR && (!SSF_ASSOC_DEFER_EMPTY || !(best < __builtin_inff()))) {
-#if SSF_ASSOC_DEFER == 2
-                if (!kSoa) {
-                    const int wq = tid >> 6;
-                    const int slot = atomicAdd(&dqnw[kSoa ? 0 : wq], 1);
-                    if (slot < kDqW) { dqw[kSoa ? 0 : wq][kSoa ? 0 : slot] = i; deferred = true; break; }
-                }
-#else
-                const int slot = atomicAdd(&dqn, 1);
-                if (slot < kDq) { dq[slot] = i; deferred = true; break; }
-#endif
-            }
-#endif
         }
         if (compact) {
             // the 1-NN's LDS position (its point and index are read back from the strips)
             const int bp = max(bc, 0), bi = v.id(bp);
             nnv[co + i] = last_valid[lo + bi] != 0 ? bp : -1 - bp;      // read back by this thread
             if (nn_out) nn_out[co + i] = bi;
-        } else if (!deferred) {
+        } else {
             assoc_finish(L, lo, last_normal, last_valid, pc, v.id(max(bc, 0)), corr, nn_out, co + i);
         }
 #ifdef SSF_ASSOC_COUNT
-        if (nn_out && !deferred) nn_out[co + i] = vis;
+        if (nn_out) nn_out[co + i] = vis;
 #endif
     }
     if (compact) {
@@ -2189,84 +1845,13 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
         }
         if (tid == 0) ncompact[p] = base;
     }
-#if SSF_ASSOC_DEFER
-    // Deferred queries, one per wave: each level R searches every strip that can hold a point
-    // within R (nominal band [qy - R - W, qy + R + W]), one strip per lane, each lane bounded by
-    // min(its best, R^2) and, from the second level on, by the wave's best; then the wave's
-    // minimum of (distance, original index).  The same exact 1-NN as the lane walk: at the level
-    // where the wave's best is <= R^2, every point at least as close was in a searched strip and
-    // within every lane's bound.
-#if SSF_ASSOC_DEFER == 2
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");             // this wave's list is complete
-    __builtin_amdgcn_wave_barrier();
-#ifdef SSF_STRIPS_STAMPS
-    const unsigned long long rtl = __builtin_amdgcn_s_memrealtime();
-#endif
-    if (kCoopG == 0 && !kSoa) {
-        constexpr int DG = kAssocDeferG;                                  // lanes per deferred query
-        const int wq = tid >> 6, lane = tid % DG;
-        const int nq = min(dqnw[kSoa ? 0 : wq], kDqW);
-        for (int e = (tid & 63) / DG; e < nq; e += 64 / DG) {
-            const int i = dqw[kSoa ? 0 : wq][kSoa ? 0 : e];               // uniform per group
-#else
-    __syncthreads();
-#ifdef SSF_STRIPS_STAMPS
-    const unsigned long long rtl = __builtin_amdgcn_s_memrealtime();   // the slowest wave's lane pass
-#endif
-    if (kCoopG == 0) {
-        constexpr int DG = kAssocDeferG;                                  // lanes per deferred query
-        const int nq = min(dqn, kDq), lane = tid % DG;
-        for (int e = tid / DG; e < nq; e += kStripThreads / DG) {
-            const int i = dq[e];                                          // uniform per group
-#endif
-            const float4 pc = curr[co + i];
-            const float4 qs = assoc_query_point(pc, q, t);
-            float best = __builtin_inff();
-            int bc = -1;
-            unsigned long long key = ~0ull;
-            for (float R = 2.0f;; R *= 2.0f) {
-                const bool unbounded = R > 4096.0f;
-                const float lim = unbounded ? __builtin_inff() : R * R;
-                const int sa = unbounded ? 0 : strip_of(qs.y - R - W - 1e-3f);
-                const int sb = unbounded ? ns - 1 : strip_of(qs.y + R + W + 1e-3f);
-                for (int sidx = sa + lane; sidx <= sb; sidx += DG) search(sidx, lim, qs, best, bc);
-                unsigned long long k = bc >= 0
-                    ? ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)v.id(bc) : ~0ull;
-#pragma unroll
-                for (int o = DG / 2; o >= 1; o >>= 1) {
-                    const unsigned long long x = __shfl_xor(k, o, kWave);
-                    k = x < k ? x : k;
-                }
-                key = k < key ? k : key;
-                const float wb = key == ~0ull ? __builtin_inff() : __uint_as_float((unsigned)(key >> 32));
-                if (wb <= lim || unbounded) break;
-                best = wb; bc = -1;          // the wave's bound (a tie taken later only raises a key)
-            }
-            if (lane == 0) {
-                assoc_finish(L, lo, last_normal, last_valid, pc, key == ~0ull ? v.id(0) : (int)(key & 0xffffffffu),
-                             corr, nn_out, co + i);
-#ifdef SSF_ASSOC_COUNT
-                if (nn_out) nn_out[co + i] = -1;                        // deferred (diagnostic build)
-#endif
-            }
-        }
-    }
-#endif
 #ifdef SSF_STRIPS_STAMPS
     __syncthreads();
     if (tid == 0 && nn_out) {
         const unsigned long long rt2 = __builtin_amdgcn_s_memrealtime(), mt2 = __builtin_amdgcn_s_memtime();
         int32_t* o = nn_out + co + kQpw * blockIdx.y;                // this work-group's own query slots
         o[0] = (int32_t)(rt1 - rt0); o[1] = (int32_t)(rt2 - rt0);
-#if SSF_ASSOC_DEFER
-#if SSF_ASSOC_DEFER == 1
-        o[2] = (int32_t)(rtl - rt0); o[3] = dqn;
-#else
-        o[2] = (int32_t)(rtl - rt0); o[3] = 0;
-#endif
-#else
         o[2] = (int32_t)(rt2 - rt0); o[3] = 0;
-#endif
         (void)mt1; (void)mt2;
         o[4] = (int32_t)(rt0 & 0x7fffffff); o[5] = __smid();
         o[6] = (int32_t)(strip_xyzi && strip_image_frame(ml) && strip_image_valid(strip_head + lo));
@@ -2446,9 +2031,6 @@ __global__ __launch_bounds__(kEdgeAssocThreads) void k_edge_associate(
 #define SSF_SOLVE_THREADS 256
 #endif
 constexpr int kSolveThreads = SSF_SOLVE_THREADS;
-#ifndef SSF_SOLVE_SPECIALISE
-#define SSF_SOLVE_SPECIALISE 1                   // one k_solve instantiation per solver mode (A/B: 0)
-#endif
 constexpr int kNE = 28;  // 21 (packed upper JtWJ) + 6 (JtWr) + cost
 
 SSF_DEV int pk(int u, int v) {
@@ -2461,9 +2043,6 @@ SSF_DEV int pk(int u, int v) {
 // Valid correspondences of a pair compacted (original order) into LDS once per solve, SoA floats:
 // every evaluation of the LM/GN loop then reads LDS instead of re-streaming the 48-byte records.
 constexpr int kSolveLdsCap = 4096;
-#ifndef SSF_SOLVE_COMPACT1
-#define SSF_SOLVE_COMPACT1 1                     // one-pass compaction of the correspondences (A/B: 0)
-#endif
 #ifndef SSF_SOLVE_CMP_PER
 #define SSF_SOLVE_CMP_PER 8
 #endif
@@ -2483,9 +2062,6 @@ SSF_DEV void quat_to_R(const double q[4], double R[9]) {
     R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.0 - (txx + tyy);
 }
 
-#ifndef SSF_SOLVE_RSQ
-#define SSF_SOLVE_RSQ 1                          // Cholesky pivots by refined v_rsq_f64 (A/B: 0 = sqrt + divide)
-#endif
 // 1 / sqrt(s) (s > 0, normal): v_rsq_f64 and two Newton steps, r <- r + r (1 - s r^2) / 2; the
 // pivot is d = s r (sqrt(s)) and its reciprocal r -- one short chain instead of the f64 sqrt and
 // divide expansions on the solve's critical path (every thread runs it)
@@ -2499,61 +2075,15 @@ SSF_DEV double rsq_refined(double s) {
     return r;
 }
 
-// 1 / x (x > 0, normal): v_rcp_f64 and two Newton steps, r <- r + r (1 - x r) -- the Huber
-// weight a / |r| of an outlier residual without the f64 divide expansion (within an ulp of it)
-SSF_DEV double rcp_refined(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-#pragma unroll
-    for (int it = 0; it < 2; ++it) r = __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
-    return r;
-}
-#ifndef SSF_SOLVE_HUBER_RCP
-#define SSF_SOLVE_HUBER_RCP 0                    // 1: Huber weights by refined rcp / rsq (r5l: 0.0857 vs 0.0808 ms, slower)
-#endif
-
 // The rotational Jacobian columns carry a factor 2 (the quaternion parameterisation below).
-// With SSF_SOLVE_JSCALE it is applied to the block sums instead of every correspondence: every
+// It is applied to the block sums instead of every correspondence: every
 // product and partial sum of those entries is then exactly 2 or 4 times the unscaled one (a
 // power-of-two scaling commutes with rounding), so the sums are bit-identical and each
 // correspondence saves three f64 multiplies.  kNeScale folds it into the evaluation's final x2
 // (the duplicated residual blocks): packed J^T W J entries (u, v) x4 (u, v < 3) / x2 (u < 3 <= v)
 // / x1, J^T W r entries x2 (u < 3), the cost x1 -- each times that 2.
-#ifndef SSF_SOLVE_JSCALE
-#define SSF_SOLVE_JSCALE 1
-#endif
-#if SSF_SOLVE_JSCALE
-constexpr double kJ2 = 1.0;
 __device__ constexpr double kNeScale[kNE] = {8, 8, 8, 4, 4, 4, 8, 8, 4, 4, 4, 8, 4, 4, 4, 2, 2, 2, 2, 2, 2,
                                              4, 4, 4, 2, 2, 2, 2};
-#else
-constexpr double kJ2 = 2.0;
-__device__ constexpr double kNeScale[kNE] = {2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2,
-                                             2, 2, 2, 2, 2, 2, 2};
-#endif
-#ifndef SSF_SOLVE_HF32
-#define SSF_SOLVE_HF32 0
-#endif
-// SSF_SOLVE_HF32: J^T W J (the 21 packed entries) accumulated per thread in packed f32 FMAs
-// (v_pk_fma_f32, two entries per instruction at the f32 rate) and added to the f64 sums before
-// the block reduction; the gradient J^T W r and the cost stay f64.  A GN / LM fixed point is set
-// by the f64 gradient; the f32 Hessian (~1e-7 relative per thread sum) moves the steps, not the
-// converged pose.  A/B switch.
-typedef float hf2 __attribute__((ext_vector_type(2)));
-constexpr int kHF = 11;                          // 21 entries in pk order, as pairs (+1 pad)
-SSF_DEV constexpr int pk_u(int e) { return e < 6 ? 0 : e < 11 ? 1 : e < 15 ? 2 : e < 18 ? 3 : e < 20 ? 4 : 5; }
-SSF_DEV constexpr int pk_v(int e) {
-    return e < 6 ? e : e < 11 ? e - 6 + 1 : e < 15 ? e - 11 + 2 : e < 18 ? e - 15 + 3 : e < 20 ? e - 18 + 4 : 5;
-}
-SSF_DEV void hess_f32(const float (&wj)[6], const float (&J)[6], hf2 (&H)[kHF]) {
-#pragma unroll
-    for (int p = 0; p < kHF; ++p) {
-        const int e0 = 2 * p, e1 = 2 * p + 1 < 21 ? 2 * p + 1 : 20;
-        const hf2 a = {wj[pk_u(e0)], 2 * p + 1 < 21 ? wj[pk_u(e1)] : 0.0f};
-        const hf2 b = {J[pk_v(e0)], J[pk_v(e1)]};
-        H[p] = __builtin_elementwise_fma(a, b, H[p]);
-    }
-}
-
 // Per-correspondence residual r = (R po + t - pa) . n (PlaneFeatureCost, :25-43) and its local
 // Jacobian [2 (R po x n), n]: the EigenQuaternionParameterization's 4x3 Jacobian composed with
 // the autodiff gradient (what the oracle's residual_jac spells out) reduces to that for a unit
@@ -2564,7 +2094,7 @@ SSF_DEV void hess_f32(const float (&wj)[6], const float (&J)[6], hf2 (&H)[kHF]) 
 // One correspondence's Huber-weighted contribution (x wgt: 0 for a padding slot) to the
 // normal equations ne (21 packed upper J^T W J, 6 J^T W r, cost).
 SSF_DEV void accum_corr(const double R[9], const double t[3], const double po[3], const double pa[3],
-                        const double nn[3], double wgt, double (&ne)[kNE], hf2 (&H)[kHF]) {
+                        const double nn[3], double wgt, double (&ne)[kNE]) {
     const double a = 0.1, b = 0.1 * 0.1;
     double u[3];
 #pragma unroll
@@ -2572,40 +2102,22 @@ SSF_DEV void accum_corr(const double R[9], const double t[3], const double po[3]
     const double d0 = (u[0] + t[0]) - pa[0], d1 = (u[1] + t[1]) - pa[1], d2 = (u[2] + t[2]) - pa[2];
     const double r = __builtin_fma(d2, nn[2], __builtin_fma(d1, nn[1], d0 * nn[0]));
     double J[6];
-    J[0] = kJ2 * __builtin_fma(u[1], nn[2], -u[2] * nn[1]);
-    J[1] = kJ2 * __builtin_fma(u[2], nn[0], -u[0] * nn[2]);
-    J[2] = kJ2 * __builtin_fma(u[0], nn[1], -u[1] * nn[0]);
+    J[0] = __builtin_fma(u[1], nn[2], -u[2] * nn[1]);
+    J[1] = __builtin_fma(u[2], nn[0], -u[0] * nn[2]);
+    J[2] = __builtin_fma(u[0], nn[1], -u[1] * nn[0]);
     J[3] = nn[0]; J[4] = nn[1]; J[5] = nn[2];
     const double s = r * r;
     double rho0, rho1;
     if (s > b) {
         const double rr = fabs(r);
         rho0 = 2.0 * a * rr - b;
-#if SSF_SOLVE_HUBER_RCP
-        rho1 = rr < 1e290 ? a * rcp_refined(rr) : a / rr;
-#else
         rho1 = a / rr;
-#endif
         if (rho1 < DBL_MIN) rho1 = DBL_MIN;
     } else {
         rho0 = s; rho1 = 1.0;
     }
     ne[27] = __builtin_fma(0.5 * wgt, rho0, ne[27]);
     rho1 *= wgt;
-#if SSF_SOLVE_HF32
-    {
-        float jf[6], wf[6];
-        const float rf = (float)rho1;
-#pragma unroll
-        for (int uu = 0; uu < 6; ++uu) { jf[uu] = (float)J[uu]; wf[uu] = rf * jf[uu]; }
-        hess_f32(wf, jf, H);
-#pragma unroll
-        for (int uu = 0; uu < 6; ++uu) ne[21 + uu] = __builtin_fma(rho1 * J[uu], r, ne[21 + uu]);
-        return;
-    }
-#else
-    (void)H;
-#endif
     int k = 0;
 #pragma unroll
     for (int uu = 0; uu < 6; ++uu) {             // explicit FMAs: the file is built without
@@ -2633,24 +2145,17 @@ SSF_DEV void accum_edge(const double R[9], const double t[3], const double po[3]
 #pragma unroll
         for (int j = 0; j < 3; ++j) nk[j] = (j == k ? 1.0 : 0.0) - uu[k] * uu[j];
         r[k] = __builtin_fma(d[2], nk[2], __builtin_fma(d[1], nk[1], d[0] * nk[0]));
-        J[k][0] = kJ2 * __builtin_fma(g[1], nk[2], -g[2] * nk[1]);
-        J[k][1] = kJ2 * __builtin_fma(g[2], nk[0], -g[0] * nk[2]);
-        J[k][2] = kJ2 * __builtin_fma(g[0], nk[1], -g[1] * nk[0]);
+        J[k][0] = __builtin_fma(g[1], nk[2], -g[2] * nk[1]);
+        J[k][1] = __builtin_fma(g[2], nk[0], -g[0] * nk[2]);
+        J[k][2] = __builtin_fma(g[0], nk[1], -g[1] * nk[0]);
         J[k][3] = nk[0]; J[k][4] = nk[1]; J[k][5] = nk[2];
         s = __builtin_fma(r[k], r[k], s);
     }
     double rho0, rho1;
     if (s > b) {
-#if SSF_SOLVE_HUBER_RCP
-        const double ri = s < 1e290 ? rsq_refined(s) : 1.0 / sqrt(s);
-        const double rr = s < 1e290 ? s * ri : sqrt(s);
-        rho0 = 2.0 * a * rr - b;
-        rho1 = a * ri;
-#else
         const double rr = sqrt(s);
         rho0 = 2.0 * a * rr - b;
         rho1 = a / rr;
-#endif
         if (rho1 < DBL_MIN) rho1 = DBL_MIN;
     } else {
         rho0 = s; rho1 = 1.0;
@@ -2677,20 +2182,13 @@ SSF_DEV void evaluate(const CorrRec* __restrict__ rec, int n, const double q[4],
     for (int k = 0; k < kNE; ++k) ne[k] = 0.0;
     double R[9];
     quat_to_R(q, R);
-    hf2 H[kHF];
-#pragma unroll
-    for (int k = 0; k < kHF; ++k) H[k] = hf2{0.0f, 0.0f};
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const CorrRec c = rec[i];
         if (c.valid == 0.0f) continue;
         const double po[3] = {c.po[0], c.po[1], c.po[2]}, pa[3] = {c.pa[0], c.pa[1], c.pa[2]},
                      nn[3] = {c.n[0], c.n[1], c.n[2]};
-        accum_corr(R, t, po, pa, nn, 1.0, ne, H);
+        accum_corr(R, t, po, pa, nn, 1.0, ne);
     }
-#if SSF_SOLVE_HF32
-#pragma unroll
-    for (int e = 0; e < 21; ++e) ne[e] += (double)H[e >> 1][e & 1];
-#endif
     for (int i = threadIdx.x; i < en; i += blockDim.x) {          // edge blocks (en = 0: none)
         const CorrRec c = erec[i];
         if (c.valid == 0.0f) continue;
@@ -2709,22 +2207,6 @@ SSF_DEV void evaluate(const CorrRec* __restrict__ rec, int n, const double q[4],
 #define SSF_SOLVE_STEP 2
 #endif
 constexpr int kSolveStep = SSF_SOLVE_STEP;
-#ifndef SSF_SOLVE_QDIRECT
-#define SSF_SOLVE_QDIRECT 0                      // A/B: every thread reads the warm start from global memory
-#endif
-#ifndef SSF_SOLVE_DIRECT
-#define SSF_SOLVE_DIRECT 1                       // compacted records: 1 loaded by the first evaluation, 2 copied first (A/B)
-#endif
-#ifndef SSF_SOLVE_LOADALL
-#define SSF_SOLVE_LOADALL 0                      // A/B: first evaluation requests every record of a thread at
-                                                 // once (r6zh: 23.2 k vs 15.5 k cycles, 0.070 vs 0.066 ms, slower)
-#endif
-#ifndef SSF_SOLVE_LDS_PF
-#define SSF_SOLVE_LDS_PF 0                       // 1: LDS records of the next step in flight (r6m: 0.0706 vs 0.0674 ms, slower)
-#endif
-#ifndef SSF_SOLVE_RED
-#define SSF_SOLVE_RED 2                          // 0 block_sum_rs; block_sum_db: 1 DPP one barrier, 2 DPP two, 3 shuffles two
-#endif
 template <int NW>
 SSF_DEV void evaluate(const CorrLds& C, int nv, const double q[4], const double t[3],
                       double (&ne)[kNE], double* lds, int nve = 0, int parity = 0) {
@@ -2733,63 +2215,27 @@ SSF_DEV void evaluate(const CorrLds& C, int nv, const double q[4], const double 
     double R[9];
     quat_to_R(q, R);
     const int T = blockDim.x;
-    hf2 H[kHF];
-#pragma unroll
-    for (int k = 0; k < kHF; ++k) H[k] = hf2{0.0f, 0.0f};
-#if SSF_SOLVE_LDS_PF
-    // the next step's LDS records are read while this step's are evaluated (one wave per SIMD:
-    // nothing else hides the LDS latency); clamped reads, a step past nv is never used
-    float g[kSolveStep][9];
-    if (threadIdx.x < nv) {
-#pragma unroll
-        for (int h = 0; h < kSolveStep; ++h) {
-            const int ih = min((int)threadIdx.x + h * T, nv - 1);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) { g[h][d] = C.po[d][ih]; g[h][3 + d] = C.pa[d][ih]; g[h][6 + d] = C.n[d][ih]; }
-        }
-    }
-#endif
     for (int i = threadIdx.x; i < nv; i += kSolveStep * T) {
         float f[kSolveStep][9];
-#if SSF_SOLVE_LDS_PF
-#pragma unroll
-        for (int h = 0; h < kSolveStep; ++h) {
-            const int ih = min(i + kSolveStep * T + h * T, nv - 1);
-#pragma unroll
-            for (int d = 0; d < 9; ++d) f[h][d] = g[h][d];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) { g[h][d] = C.po[d][ih]; g[h][3 + d] = C.pa[d][ih]; g[h][6 + d] = C.n[d][ih]; }
-        }
-#else
 #pragma unroll
         for (int h = 0; h < kSolveStep; ++h) {
             const int ih = min(i + h * T, nv - 1);
 #pragma unroll
             for (int d = 0; d < 3; ++d) { f[h][d] = C.po[d][ih]; f[h][3 + d] = C.pa[d][ih]; f[h][6 + d] = C.n[d][ih]; }
         }
-#endif
 #pragma unroll
         for (int h = 0; h < kSolveStep; ++h) {
             const double po[3] = {f[h][0], f[h][1], f[h][2]}, pa[3] = {f[h][3], f[h][4], f[h][5]},
                          nn[3] = {f[h][6], f[h][7], f[h][8]};
-            accum_corr(R, t, po, pa, nn, (h == 0 || i + h * T < nv) ? 1.0 : 0.0, ne, H);
+            accum_corr(R, t, po, pa, nn, (h == 0 || i + h * T < nv) ? 1.0 : 0.0, ne);
         }
     }
-#if SSF_SOLVE_HF32
-#pragma unroll
-    for (int e = 0; e < 21; ++e) ne[e] += (double)H[e >> 1][e & 1];
-#endif
     for (int i = nv + threadIdx.x; i < nv + nve; i += T) {        // edge blocks after the planes
         const double po[3] = {C.po[0][i], C.po[1][i], C.po[2][i]}, pa[3] = {C.pa[0][i], C.pa[1][i], C.pa[2][i]},
                      uu[3] = {C.n[0][i], C.n[1][i], C.n[2][i]};
         accum_edge(R, t, po, pa, uu, 1.0, ne);
     }
-#if SSF_SOLVE_RED == 0
-    (void)parity;
-    block_sum_rs<kNE>(ne, lds);
-#else
-    block_sum_db<kNE, NW, SSF_SOLVE_RED != 3, SSF_SOLVE_RED == 1>(ne, lds, parity);
-#endif
+    block_sum_db<kNE, NW>(ne, lds, parity);
 #pragma unroll
     for (int k = 0; k < kNE; ++k) ne[k] *= kNeScale[k];
 }
@@ -2808,41 +2254,6 @@ SSF_DEV void evaluate_load(const CorrRec* __restrict__ rec, CorrLds& C, int nv, 
     double R[9];
     quat_to_R(q, R);
     const int T = blockDim.x;
-    hf2 H[kHF];
-#pragma unroll
-    for (int k = 0; k < kHF; ++k) H[k] = hf2{0.0f, 0.0f};
-#if SSF_SOLVE_LOADALL
-    // every record of this thread (<= kSolveLdsCap / T of them) requested at once into registers
-    // (one wave per SIMD: 512 VGPRs per lane to spend, and nothing else hides a load's latency),
-    // then the same steps in the same order as below; clamped, unconditional loads
-    constexpr int kR = kSolveLdsCap / (NW * 64);
-    static_assert(kR % kSolveStep == 0, "whole steps");
-    float4 a0[kR], a1[kR], a2[kR];
-#pragma unroll
-    for (int k = 0; k < kR; ++k) {
-        const float4* rp = reinterpret_cast<const float4*>(rec + min((int)threadIdx.x + k * T, nv - 1));
-        a0[k] = rp[0]; a1[k] = rp[1]; a2[k] = rp[2];
-    }
-#pragma unroll
-    for (int s0 = 0; s0 < kR; s0 += kSolveStep) {
-        const int i = (int)threadIdx.x + s0 * T;
-        if (i < nv) {
-#pragma unroll
-            for (int h = 0; h < kSolveStep; ++h) {
-                const int ih = i + h * T;
-                const int k = s0 + h;
-                if (ih < nv) {
-                    C.po[0][ih] = a0[k].x; C.po[1][ih] = a0[k].y; C.po[2][ih] = a0[k].z;
-                    C.pa[0][ih] = a1[k].x; C.pa[1][ih] = a1[k].y; C.pa[2][ih] = a1[k].z;
-                    C.n[0][ih] = a2[k].x; C.n[1][ih] = a2[k].y; C.n[2][ih] = a2[k].z;
-                }
-                const double po[3] = {a0[k].x, a0[k].y, a0[k].z}, pa[3] = {a1[k].x, a1[k].y, a1[k].z},
-                             nn[3] = {a2[k].x, a2[k].y, a2[k].z};
-                accum_corr(R, t, po, pa, nn, (h == 0 || ih < nv) ? 1.0 : 0.0, ne, H);
-            }
-        }
-    }
-#else
     // one step's records in flight ahead of the step being evaluated (clamped, unconditional
     // loads: a step past nv re-reads record nv - 1 and is never used)
     float4 n0[kSolveStep], n1[kSolveStep], n2[kSolveStep];
@@ -2869,20 +2280,10 @@ SSF_DEV void evaluate_load(const CorrRec* __restrict__ rec, CorrLds& C, int nv, 
             }
             const double po[3] = {r0[h].x, r0[h].y, r0[h].z}, pa[3] = {r1[h].x, r1[h].y, r1[h].z},
                          nn[3] = {r2[h].x, r2[h].y, r2[h].z};
-            accum_corr(R, t, po, pa, nn, (h == 0 || ih < nv) ? 1.0 : 0.0, ne, H);
+            accum_corr(R, t, po, pa, nn, (h == 0 || ih < nv) ? 1.0 : 0.0, ne);
         }
     }
-#endif
-#if SSF_SOLVE_HF32
-#pragma unroll
-    for (int e = 0; e < 21; ++e) ne[e] += (double)H[e >> 1][e & 1];
-#endif
-#if SSF_SOLVE_RED == 0
-    (void)parity;
-    block_sum_rs<kNE>(ne, lds);
-#else
-    block_sum_db<kNE, NW, SSF_SOLVE_RED != 3, SSF_SOLVE_RED == 1>(ne, lds, parity);
-#endif
+    block_sum_db<kNE, NW>(ne, lds, parity);
 #pragma unroll
     for (int k = 0; k < kNE; ++k) ne[k] *= kNeScale[k];
 }
@@ -2892,9 +2293,8 @@ SSF_DEV void evaluate_load(const CorrRec* __restrict__ rec, CorrLds& C, int nv, 
 // cos on the per-iteration critical path every thread runs.  The first omitted terms are below
 // 2^-95 (sinc, x2^5 / 11!) and 2^-112 (cos, x2^6 / 12!) of the results, far under one f64 ulp
 // (2^-53): the values agree with libm's to an ulp or so, as libm agrees with the oracle's glibc.
-// Larger steps take quat_plus itself.  -DSSF_QUAT_PLUS_LIBM restores libm everywhere (A/B).
+// Larger steps take quat_plus itself.
 SSF_DEV void quat_plus_step(const double q[4], const double d[3], double o[4]) {
-#ifndef SSF_QUAT_PLUS_LIBM
     const double x2 = __builtin_fma(d[2], d[2], __builtin_fma(d[1], d[1], d[0] * d[0]));
     if (x2 > 0.0 && x2 < 0x1p-14) {
         // Horner in x2: sinc = sum (-x2)^k / (2k + 1)!, k <= 4; cos = sum (-x2)^k / (2k)!, k <= 5
@@ -2913,51 +2313,15 @@ SSF_DEV void quat_plus_step(const double q[4], const double d[3], double o[4]) {
         quat_mul(dq, q, o);
         return;
     }
-#endif
     quat_plus(q, d, o);
-}
-
-SSF_DEV int chol_solve6(double M[6][6], const double b[6], double y[6]) {
-    double L[6][6];
-    for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) L[i][j] = 0.0;
-    for (int j = 0; j < 6; ++j) {
-        double s = M[j][j];
-        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-        if (!(s > 0.0)) return -1;
-        L[j][j] = sqrt(s);
-        for (int i = j + 1; i < 6; ++i) {
-            double v = M[i][j];
-            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-            L[i][j] = v / L[j][j];
-        }
-    }
-    double z[6];
-    for (int i = 0; i < 6; ++i) {
-        double v = b[i];
-        for (int k = 0; k < i; ++k) v -= L[i][k] * z[k];
-        z[i] = v / L[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double v = z[i];
-        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * y[k];
-        y[i] = v / L[i][i];
-    }
-    return 0;
 }
 
 // Cholesky solve of the packed symmetric normal equations A y = -g (A = ne[0..20] upper packed,
 // g = ne[21..26]): 21 + 21 doubles of state, one reciprocal per diagonal instead of a division
 // per element (the GN path runs it redundantly on every thread).
-#ifndef SSF_SOLVE_CHOL_FMA
-#define SSF_SOLVE_CHOL_FMA 1                     // the 6x6 solve's multiply-subtracts as FMAs (A/B: 0)
-#endif
 // a - b c, as one fused operation (a shorter dependent chain; the step moves by rounding only)
 SSF_DEV double msub(double a, double b, double c) {
-#if SSF_SOLVE_CHOL_FMA
     return __builtin_fma(-b, c, a);
-#else
-    return a - b * c;
-#endif
 }
 SSF_DEV int chol_solve_packed(const double (&ne)[kNE], double y[6]) {
     double L[21];                         // L(i, j), j <= i, at pk(j, i)
@@ -2968,14 +2332,9 @@ SSF_DEV int chol_solve_packed(const double (&ne)[kNE], double y[6]) {
 #pragma unroll
         for (int k = 0; k < j; ++k) s = msub(s, L[pk(k, j)], L[pk(k, j)]);
         if (!(s > 0.0)) return -1;
-#if SSF_SOLVE_RSQ
         const double r = (s > 1e-290 && s < 1e290) ? rsq_refined(s) : 1.0 / sqrt(s);
         const double d = (s > 1e-290 && s < 1e290) ? s * r : sqrt(s);
         inv[j] = r;
-#else
-        const double d = sqrt(s);
-        inv[j] = 1.0 / d;
-#endif
         L[pk(j, j)] = d;
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
@@ -3003,12 +2362,9 @@ SSF_DEV int chol_solve_packed(const double (&ne)[kNE], double y[6]) {
     return 0;
 }
 
-struct SolveShared {
-    double q[4], t[3], qc[4], tc[3];
-    double s[6];
-    double ne[kNE];       // normal equations at the current x
-    double radius, dec, mcc;
-    int invalid, flag, nlog, done;
+struct SolveShared {       // the pair's pose and log length, from the solve to thread 0's output
+    double q[4], t[3];
+    int nlog;
 };
 
 SSF_DEV void write_log(double* log, int max_iter, int p, int idx, const double q[4],
@@ -3020,20 +2376,17 @@ SSF_DEV void write_log(double* log, int max_iter, int p, int idx, const double q
     r[7] = cost; r[8] = status; r[9] = radius;
 }
 
-#ifndef SSF_SOLVE_LM_REG
-#define SSF_SOLVE_LM_REG 1                       // LM state in every thread's registers (A/B: 0 = lane-0 step)
-#endif
 // kEdges: point-to-line blocks (ecorr at ecurr_off / ecurr_count) join every evaluation; they
 // are compacted into the same LDS arrays after the planes.
 // kMode: the solver this instantiation runs (SSF_SOLVER_GN / SSF_SOLVER_CERES_LM), so each mode's
-// register allocation covers its own loop only (the LM state does not weigh on the GN kernel);
-// -1 dispatches on the runtime `mode` (A/B: SSF_SOLVE_SPECIALISE=0).
+// register allocation covers its own loop only (the LM state does not weigh on the GN kernel).
+// The launch still passes the mode as an argument; the kernel does not read it.
 template <bool kEdges, int NT, int kMode>
 __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
                                                          const int64_t* __restrict__ curr_off,
                                                          const int32_t* __restrict__ curr_count,
                                                          const int32_t* __restrict__ last_count,
-                                                         int mode, int max_iter,
+                                                         int /*mode*/, int max_iter,
                                                          const double* pose_in,
                                                          const double* pose_abs_in,
                                                          double* pose_rel,
@@ -3049,11 +2402,7 @@ __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
     __shared__ SolveShared S;
     __shared__ double red[2 * (NT / 64 + 1) * kNE];                   // block_sum_db: two halves
     __shared__ CorrLds C;
-#if SSF_SOLVE_COMPACT1
     __shared__ int wtot2[2][NT / 64];
-#else
-    __shared__ int wtot[NT / 64];
-#endif
     const int p = blockIdx.x, tid = threadIdx.x;
     const int n = curr_count[p];
     const CorrRec* rec = corr + curr_off[p];
@@ -3075,18 +2424,14 @@ __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
     if (tid == 0) {
         for (int k = 0; k < 4; ++k) S.q[k] = pose_in[7 * p + k];
         for (int k = 0; k < 3; ++k) S.t[k] = pose_in[7 * p + 4 + k];
-        S.nlog = 0; S.done = 0;
+        S.nlog = 0;
     }
     __syncthreads();
     const bool skip = last_count[p] <= 10;                              // :158
     if (!skip) {
-        // order-preserving compaction of the valid records into LDS, coalesced: record i goes
-        // to thread i % T in trip i / T; per trip a ballot + the wave counts give every valid
-        // record its rank.  kPre trips' records are loaded before the first is used (one load
-        // latency per kPre trips).
+        // order-preserving compaction of the valid records into LDS, coalesced:
         const int lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
         const int T = blockDim.x;
-#if SSF_SOLVE_COMPACT1
         // one pass per kCmpPer x T records: wave w takes a contiguous range of kCmpPer x 64, every
         // load of the pass in flight at once; per 64-record step a ballot, the ranks from the
         // wave's own popcounts and ONE exchange of the wave totals (one barrier per pass; the
@@ -3129,35 +2474,6 @@ __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
             __syncthreads();                                            // the LDS records, for every wave
             return nv;
         };
-#else
-        constexpr int kPre = 2;
-        // records [0, cnt) of src appended at LDS position `start`; returns the valid count
-        auto compact = [&](const CorrRec* __restrict__ src, int cnt, int start) {
-            int nv = 0;                                                 // uniform
-            for (int i0 = 0; i0 < cnt; i0 += kPre * T) {
-                CorrRec c[kPre];
-#pragma unroll
-                for (int k = 0; k < kPre; ++k) c[k] = src[min(i0 + k * T + tid, cnt - 1)];   // clamped
-#pragma unroll
-                for (int k = 0; k < kPre; ++k) {
-                    const bool v = i0 + k * T + tid < cnt && c[k].valid != 0.0f;
-                    const uint64_t m = __ballot(v);
-                    if (lane == 0) wtot[w] = __popcll(m);
-                    __syncthreads();
-                    int before = start + nv, tot = 0;
-                    for (int j = 0; j < nw; ++j) { const int x = wtot[j]; if (j < w) before += x; tot += x; }
-                    const int pos = before + __popcll(m & lanemask_lt());
-                    if (v && pos < kSolveLdsCap) {
-#pragma unroll
-                        for (int d = 0; d < 3; ++d) { C.po[d][pos] = c[k].po[d]; C.pa[d][pos] = c[k].pa[d]; C.n[d][pos] = c[k].n[d]; }
-                    }
-                    nv += tot;
-                    __syncthreads();                                    // wtot is rewritten next trip
-                }
-            }
-            return nv;
-        };
-#endif
         // compacted records: [0, ncp) in rank order, streamed into LDS by the first evaluation
         // itself (evaluate_load: the same per-thread order and sums as evaluate() from LDS), no
         // ballot pass
@@ -3179,55 +2495,20 @@ __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
         };
         double ne[kNE];
         double q[4], t[3];
-#if SSF_SOLVE_QDIRECT
-        for (int k = 0; k < 4; ++k) q[k] = pose_in[7 * p + k];                 // (A/B) uniform loads
-        for (int k = 0; k < 3; ++k) t[k] = pose_in[7 * p + 4 + k];
-#else
         for (int k = 0; k < 4; ++k) q[k] = S.q[k];
         for (int k = 0; k < 3; ++k) t[k] = S.t[k];
-#endif
         // (nv == 0 -- an empty current frame, or no valid correspondence -- has no record to load:
         // evaluate_load's clamped loads would read rec[-1]; evaluate() from LDS gives the zero sums)
-        if (ncp > 0 && in_lds && SSF_SOLVE_DIRECT == 1) {
+        if (ncp > 0 && in_lds) {
             evaluate_load<NT / 64>(rec, C, nv, q, t, ne, red, par);
             par ^= 1;
         } else {
-            if (ncp > 0 && in_lds && SSF_SOLVE_DIRECT != 1) {
-                // (A/B, SSF_SOLVE_DIRECT=2) a plain copy of the compacted records into LDS, four
-                // per thread in flight: thread t writes the positions t + k T it reads itself
-                const int T = blockDim.x;
-                for (int i0 = tid; i0 < nv; i0 += 4 * T) {
-                    float4 a[4][3];
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) {
-                        const float4* rp = reinterpret_cast<const float4*>(rec + min(i0 + h * T, nv - 1));
-                        a[h][0] = rp[0]; a[h][1] = rp[1]; a[h][2] = rp[2];
-                    }
-#pragma unroll
-                    for (int h = 0; h < 4; ++h) {
-                        const int ih = i0 + h * T;
-                        if (ih < nv) {
-                            C.po[0][ih] = a[h][0].x; C.po[1][ih] = a[h][0].y; C.po[2][ih] = a[h][0].z;
-                            C.pa[0][ih] = a[h][1].x; C.pa[1][ih] = a[h][1].y; C.pa[2][ih] = a[h][1].z;
-                            C.n[0][ih] = a[h][2].x; C.n[1][ih] = a[h][2].y; C.n[2][ih] = a[h][2].z;
-                        }
-                    }
-                }
-            }
             eval_at(q, t, ne);
         }
 #ifdef SSF_SOLVE_STAMPS
         st2 = __builtin_amdgcn_s_memtime();
 #endif
-#if !SSF_SOLVE_LM_REG
-        if (tid == 0) {
-            for (int k = 0; k < kNE; ++k) S.ne[k] = ne[k];
-            for (int u = 0; u < 6; ++u) S.s[u] = 1.0 / (1.0 + sqrt(ne[pk(u, u)]));
-            S.radius = 1e4; S.dec = 2.0; S.invalid = 0;
-        }
-        __syncthreads();
-#endif
-        if ((kMode >= 0 ? kMode : mode) == SSF_SOLVER_GN) {
+        if (kMode == SSF_SOLVER_GN) {
             // every thread holds the same sums after the block reduction, so every thread runs
             // the same 6x6 solve on the same bits and carries the same pose: no lane-0 step, no
             // LDS broadcast, no extra barrier per iteration (thread 0 alone writes the log)
@@ -3265,7 +2546,6 @@ __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
             }
             __syncthreads();
         } else {
-#if SSF_SOLVE_LM_REG
             // every thread carries the LM state (accepted pose and normal equations, scaling,
             // radius) in registers and runs the same step on the same bits, as the GN path does:
             // no lane-0 section that the other 255 threads wait on at two barriers per iteration,
@@ -3374,102 +2654,6 @@ __global__ __launch_bounds__(NT) void k_solve(const CorrRec* __restrict__ corr,
                 for (int k = 0; k < 3; ++k) S.t[k] = ta[k];
                 S.nlog = nl;
             }
-#else
-            for (int it = 1; it <= max_iter; ++it) {
-                if (tid == 0) {
-                    // LevenbergMarquardtStrategy::ComputeStep on the Jacobi-scaled system
-                    double As[6][6], gs[6], M[6][6], bb[6], y[6];
-                    for (int u = 0; u < 6; ++u) {
-                        gs[u] = S.s[u] * S.ne[21 + u];
-                        for (int v = 0; v < 6; ++v) As[u][v] = S.s[u] * S.ne[pk(u, v)] * S.s[v];
-                    }
-                    for (int u = 0; u < 6; ++u) {
-                        double d = As[u][u];
-                        if (d < 1e-6) d = 1e-6;
-                        if (d > 1e32) d = 1e32;
-                        for (int v = 0; v < 6; ++v) M[u][v] = As[u][v];
-                        M[u][u] += d / S.radius;
-                        bb[u] = -gs[u];
-                    }
-                    const bool ok = chol_solve6(M, bb, y) == 0;
-                    double mcc = 0.0;
-                    if (ok) {
-                        double yg = 0.0, yAy = 0.0;
-                        for (int u = 0; u < 6; ++u) {
-                            yg += y[u] * gs[u];
-                            double Ay = 0.0;
-                            for (int v = 0; v < 6; ++v) Ay += As[u][v] * y[v];
-                            yAy += y[u] * Ay;
-                        }
-                        mcc = -(yg + 0.5 * yAy);
-                    }
-                    if (!ok || !(mcc > 0.0)) {
-                        S.radius /= S.dec; S.dec *= 2.0;
-                        write_log(log, max_iter, p, S.nlog++, S.q, S.t, S.ne[27], 2, S.radius);
-                        S.flag = 0;
-                        if (++S.invalid > 5) S.done = 1;
-                    } else {
-                        S.invalid = 0;
-                        double delta[6];
-                        for (int u = 0; u < 6; ++u) delta[u] = y[u] * S.s[u];
-                        quat_plus(S.q, delta, S.qc);
-                        S.tc[0] = S.t[0] + delta[3]; S.tc[1] = S.t[1] + delta[4]; S.tc[2] = S.t[2] + delta[5];
-                        S.mcc = mcc;
-                        S.flag = 1;
-                    }
-                }
-                __syncthreads();
-                if (S.done) break;
-                if (!S.flag) continue;
-                double qc[4], tc[3];
-                for (int k = 0; k < 4; ++k) qc[k] = S.qc[k];
-                for (int k = 0; k < 3; ++k) tc[k] = S.tc[k];
-                eval_at(qc, tc, ne);
-                if (tid == 0) {
-                    double xn = 0.0, sn = 0.0;
-                    for (int u = 0; u < 4; ++u) { xn += S.q[u] * S.q[u]; sn += (S.q[u] - S.qc[u]) * (S.q[u] - S.qc[u]); }
-                    for (int u = 0; u < 3; ++u) { xn += S.t[u] * S.t[u]; sn += (S.t[u] - S.tc[u]) * (S.t[u] - S.tc[u]); }
-                    xn = sqrt(xn); sn = sqrt(sn);
-                    const double dcost = S.ne[27] - ne[27];
-                    if (!(sn > (xn + 1e-8) * 1e-8)) {                   // ParameterToleranceReached
-                        write_log(log, max_iter, p, S.nlog++, S.q, S.t, S.ne[27], 3, S.radius);
-                        S.done = 1;
-                    } else if (!(fabs(dcost) > 1e-6 * S.ne[27])) {      // FunctionToleranceReached
-                        write_log(log, max_iter, p, S.nlog++, S.q, S.t, S.ne[27], 4, S.radius);
-                        S.done = 1;
-                    } else {
-                        const double rho = dcost / S.mcc;
-                        if (rho > 1e-3) {                               // accept
-                            for (int k = 0; k < 4; ++k) S.q[k] = S.qc[k];
-                            for (int k = 0; k < 3; ++k) S.t[k] = S.tc[k];
-                            for (int k = 0; k < kNE; ++k) S.ne[k] = ne[k];
-                            const double f = 2.0 * rho - 1.0;
-                            double den = 1.0 - f * f * f;
-                            if (den < 1.0 / 3.0) den = 1.0 / 3.0;
-                            S.radius = S.radius / den;
-                            if (S.radius > 1e16) S.radius = 1e16;
-                            S.dec = 2.0;
-                            const double mg[3] = {-ne[21], -ne[22], -ne[23]};
-                            double qg[4], gm = 0.0;
-                            quat_plus(S.q, mg, qg);
-                            for (int u = 0; u < 4; ++u) gm = fmax(gm, fabs(S.q[u] - qg[u]));
-                            for (int u = 3; u < 6; ++u) gm = fmax(gm, fabs(ne[21 + u]));
-                            if (gm <= 1e-10) {
-                                write_log(log, max_iter, p, S.nlog++, S.q, S.t, S.ne[27], 5, S.radius);
-                                S.done = 1;
-                            } else {
-                                write_log(log, max_iter, p, S.nlog++, S.q, S.t, S.ne[27], 1, S.radius);
-                            }
-                        } else {                                        // reject
-                            S.radius /= S.dec; S.dec *= 2.0;
-                            write_log(log, max_iter, p, S.nlog++, S.q, S.t, S.ne[27], 0, S.radius);
-                        }
-                    }
-                }
-                __syncthreads();
-                if (S.done) break;
-            }
-#endif
         }
     } else if (tid == 0) {
         if (ncorr_out) ncorr_out[p] = -1;
@@ -3562,27 +2746,22 @@ hipError_t launch_plane_table(hipStream_t s, const ssf_config& cfg, int n_frames
 // work-groups per pair, each staging the last frame and taking a share of the queries, so the
 // launch spreads over ~256 CUs instead of n_pairs (every work-group stages the whole last frame,
 // so the split is capped at ~4 launch-filling waves of work-groups; the query loop strides over
-// gridDim.y).  Big launches: the lane mode (or SSF_ASSOC_BIG_G-lane groups, A/B), split over
+// gridDim.y).  Big launches: the lane mode, split over
 // min(8, 256 / n_pairs, ceil(max_m / kStripThreads)) work-groups per pair; with ONE work-group
 // per pair and planes only, the association hands the solve compacted records.
 RegisterPlan register_plan(int n_pairs, int64_t max_m, bool with_edges) {
     RegisterPlan r{};
-#ifndef SSF_ASSOC_XBAND
     if (n_pairs <= 0 || max_m <= 0 || max_m > kSortMax) return r;
     r.strips = true;
     r.soa = max_m > kAssocStripF4Max;
     r.lds_cap = (int)std::min<int64_t>(max_m, r.soa ? kAssocStripSoaMax : kAssocStripF4Max);
-    r.coop = kAssocCoopG > 0 && n_pairs <= kAssocCoopPairs;
-    r.bigc = !r.coop && kAssocBigG > 0;
-    constexpr int kQpwCoop = kAssocCoopG > 0 ? kStripThreads / kAssocCoopG : kStripThreads;
+    r.coop = n_pairs <= kAssocCoopPairs;
+    constexpr int kQpwCoop = kStripThreads / kAssocCoopG;
     r.qsplit = r.coop ? (int)std::min<int64_t>((max_m + kQpwCoop - 1) / kQpwCoop,
                                                std::max(8, 1024 / n_pairs))
                       : (int)std::max<int64_t>(1, std::min<int64_t>({8, 256 / n_pairs,
                                                (max_m + kStripThreads - 1) / kStripThreads}));
-    r.compacted = !r.coop && !r.bigc && r.qsplit == 1 && !with_edges && !SSF_ASSOC_DEFER && SSF_ASSOC_COMPACT;
-#else
-    (void)n_pairs; (void)max_m; (void)with_edges;
-#endif
+    r.compacted = !r.coop && r.qsplit == 1 && !with_edges;
     return r;
 }
 
@@ -3608,33 +2787,18 @@ hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, co
         const int bx = (int)((max_m + 255) / 256);
         const RegisterPlan plan = register_plan(n_pairs, max_m, edge != nullptr);
         if (plan.strips && last_sorted && last_sidx) {
-            const bool soa = plan.soa, coop = plan.coop, bigc = plan.bigc;
+            const bool soa = plan.soa, coop = plan.coop;
             const int cap = plan.lds_cap, qsplit = plan.qsplit;
             const size_t lds = soa ? (size_t)cap * 14 + 16 : (size_t)cap * sizeof(float4);
             if (plan.compacted && nnv && ncompact) ncp = ncompact;
             kmark(s, coop ? "k_associate_strips_coop" : soa ? "k_associate_strips_soa" : "k_associate_strips");
             hipLaunchKernelGGL(coop ? (soa ? k_associate_strips<true, kAssocCoopG> : k_associate_strips<false, kAssocCoopG>)
-                                    : bigc ? (soa ? k_associate_strips<true, kAssocBigG> : k_associate_strips<false, kAssocBigG>)
                                     : (soa ? k_associate_strips<true> : k_associate_strips<false>),
                                dim3(n_pairs, qsplit), dim3(kStripThreads), lds, s, last, last_off, last_count,
                                last_normal, last_valid, last_sorted, last_sidx, curr, curr_off,
                                curr_count, pin, corr, nn, cap,
                                last_strip_head ? last_strip_xyzi : nullptr, last_strip_head,
                                ncp ? nnv : nullptr, ncp);
-        } else if (max_m <= kAssocSoaMax && last_sorted && last_sidx) {
-            const int qx = (int)((max_m + kAssocQ - 1) / kAssocQ);
-            const bool soa = max_m > kAssocLdsMax;
-            kmark(s, soa ? "k_associate_lds_soa" : "k_associate_lds");
-            const size_t lds = (size_t)max_m * (soa ? 12 : sizeof(float4)) + kAssocQ * sizeof(int);
-            hipLaunchKernelGGL(soa ? k_associate_lds<true> : k_associate_lds<false>,
-                               dim3(qx, n_pairs), dim3(kAssocThreads), lds, s, last, last_off,
-                               last_count, last_normal, last_valid, last_sorted, last_sidx, curr,
-                               curr_off, curr_count, pin, corr, nn, (int)max_m);
-        } else if (max_m <= kSortMax && last_sorted && last_sidx) {
-            kmark(s, "k_associate_sorted");
-            hipLaunchKernelGGL(k_associate_sorted, dim3(bx, n_pairs), dim3(256), 0, s, last, last_off,
-                               last_count, last_normal, last_valid, last_sorted, last_sidx, curr,
-                               curr_off, curr_count, pin, corr, nn);
         } else {
             kmark(s, "k_associate");
             hipLaunchKernelGGL(k_associate, dim3(bx, n_pairs), dim3(256), 0, s, last, last_off,
@@ -3651,18 +2815,11 @@ hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, co
                            edge->corr, cap);
     }
     kmark(s, "k_solve");
-#if SSF_SOLVE_SPECIALISE
 #define SSF_SOLVE_LAUNCH(E, NT, ...)                                                               \
     hipLaunchKernelGGL((cfg.solver == SSF_SOLVER_GN ? k_solve<E, NT, SSF_SOLVER_GN> : k_solve<E, NT, SSF_SOLVER_CERES_LM>), \
                        dim3(n_pairs), dim3(NT), 0, s, corr, curr_off, curr_count, \
                        last_count, cfg.solver, cfg.max_iter, pin, ain, pose_rel, pose_abs, log, nlog, ncorr, \
                        __VA_ARGS__, ncp)
-#else
-#define SSF_SOLVE_LAUNCH(E, NT, ...)                                                               \
-    hipLaunchKernelGGL((k_solve<E, NT, -1>), dim3(n_pairs), dim3(NT), 0, s, corr, curr_off, curr_count, \
-                       last_count, cfg.solver, cfg.max_iter, pin, ain, pose_rel, pose_abs, log, nlog, ncorr, \
-                       __VA_ARGS__, ncp)
-#endif
     if (edge)
         SSF_SOLVE_LAUNCH(true, kSolveThreads, edge->corr, edge->curr_off, edge->curr_count, edge->ncorr);
     else

@@ -141,7 +141,6 @@ hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, co
 struct RegisterPlan {
     bool strips;      // k_associate_strips (max_m <= the LDS sort limit)
     bool coop;        // group mode: one query per lane group, qsplit work-groups per pair
-    bool bigc;        // (A/B build only) lane groups for big launches too
     bool soa;         // 14-B SoA staging instead of float4
     bool compacted;   // the association writes compacted records and the solve streams them in
     int qsplit;       // work-groups per pair

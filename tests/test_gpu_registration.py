@@ -353,10 +353,10 @@ def test_16_row_profile_table_and_registration(oracle, dev):
 
 @pytest.mark.parametrize("k", [2, 3, 4])
 def test_associate_large_frames(oracle, dev, k):
-    """1-NN indices exact above the 16-B LDS staging size (6144 plane points): k = 2, 3 stage the
-    last frame as 12-B SoA arrays (<= 12032, ties resolved through the global permutation), k = 4
-    walks the sorted last frame in global memory.  The last frame holds exact duplicates, so
-    distance ties occur and must resolve to the lower original index."""
+    """1-NN indices exact above the 16-B LDS staging size (6144 plane points): k = 2 stages the
+    last frame as 14-B SoA strips (x | y | z floats + a u16 original index, <= 10752 points),
+    k = 3, 4 walk the sorted last frame in global memory.  The last frame holds exact duplicates,
+    so distance ties occur and must resolve to the lower original index."""
     import ssf
     rng = np.random.default_rng(11 + k)
     base = [oracle.extract_planes(frame(s, 0, n_az=1875)[0], 64) for s in range(k + 1)]
@@ -364,7 +364,7 @@ def test_associate_large_frames(oracle, dev, k):
     L = np.concatenate([L, L[rng.choice(len(L), 300, replace=False)]])
     L = L[rng.permutation(len(L))]
     Cc = np.concatenate(base[1:])
-    assert 6144 < len(L) and (len(L) <= 12032) == (k < 4) and len(L) <= 16384
+    assert 6144 < len(L) and (len(L) <= 10752) == (k < 3) and len(L) <= 16384
     fe = ssf.Frontend(64, device=dev.index)
     sizes = [len(L), len(Cc)]
     off, h_off = ssf.frame_offsets(sizes, dev)

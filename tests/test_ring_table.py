@@ -183,7 +183,7 @@ def test_chains_differ_only_near_bin_edges(oracle, n_rows):
 @pytest.mark.parametrize("chain", ["float", "double"])
 @pytest.mark.parametrize("n_rows", [64, 16])
 def test_row_intervals_hold_exactly_their_row(oracle, n_rows, chain):
-    """k_feat_wave_reg (and k_feat_chunk_reg) accept a point for the lane's row when its fast
+    """k_feat_wave_reg accepts a point for the lane's row when its fast
     ratio lies inside the row's [lo, hi) shrunk by m = 1e-6 max(1, |lo|, |hi|): every ratio within
     4e-7 (relative: the fast ratio's error) of that shrunk interval has the row's reference id;
     float chain: lo / hi are exact (the float below lo and the float at hi are other rows)"""

@@ -1,6 +1,6 @@
 """Kernel-only times of the frameFeature chain (+ plane table, association, solve) on B synthetic
 frames, through one Frontend context with ssf_profile_enable, on one stream.  Compare library
-variants by running it under different SSF_LIB (build.py build_variant).
+variants by running it under different SSF_LIB.
 
     python tools/bench_features.py [--batch 256] [--n-az 1875] [--reps 5] [--distinct 16]
 """

@@ -1,6 +1,7 @@
-"""Phase-1 walk lengths of k_associate_lds per query (diagnostic build -DSSF_ASSOC_COUNT, loaded
-through SSF_LIB): mean / percentiles per query, and the per-wave maximum (64 consecutive queries)
-that sets a wave's time."""
+"""Walk lengths of k_associate_strips per query (diagnostic build -DSSF_ASSOC_COUNT, loaded through
+SSF_LIB; nn then holds the candidates visited in its low half and the strip searches above):
+mean / percentiles per query, and the per-wave maximum (64 consecutive queries) that sets a
+wave's time."""
 import os
 import sys
 
@@ -31,13 +32,11 @@ def main():
     cnt = pb[1].count.cpu().numpy()
     si = ctab[3].cpu().numpy()
     curr = pb[1].xyzi.cpu().numpy()
-    vis, wmax, wmean, p2 = [], [], [], 0
+    vis, wmax, wmean = [], [], []
     xmax, xmean, ymax, ymean = [], [], [], []
     for p in range(B):
         o = int(h_off[p])
-        v = nn[o:o + cnt[p]].astype(np.int64)
-        p2 += int((v < 0).sum())
-        v = np.where(v < 0, -1 - v, v)
+        v = nn[o:o + cnt[p]].astype(np.int64) & 0xffff
         vis.append(v)
         for w0 in range(0, len(v), 64):
             wmax.append(v[w0:w0 + 64].max()); wmean.append(v[w0:w0 + 64].mean())
@@ -49,8 +48,7 @@ def main():
             ymax.append(vy[w0:w0 + 64].max()); ymean.append(vy[w0:w0 + 64].mean())
     a = np.concatenate(vis)
     print(f"queries {len(a)}: visited mean {a.mean():.1f} p50 {np.percentile(a, 50):.0f} "
-          f"p90 {np.percentile(a, 90):.0f} p99 {np.percentile(a, 99):.0f} max {a.max()} | "
-          f"phase 2 {p2} ({100.0 * p2 / len(a):.1f} %)")
+          f"p90 {np.percentile(a, 90):.0f} p99 {np.percentile(a, 99):.0f} max {a.max()}")
     wmax, wmean = np.array(wmax), np.array(wmean)
     print(f"waves {len(wmax)}: per-wave max mean {wmax.mean():.1f} (x{wmax.mean() / a.mean():.2f} the mean "
           f"query), lane efficiency {wmean.sum() / wmax.sum():.3f}")

@@ -3,7 +3,7 @@
     rocprofv3 --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 \
         SQ_INSTS_VALU_TRANS_F64 --output-format csv -d gpurun_out/pmc_f64 -o d -- python bench.py --serial ...
     python tools/pmc_f64.py gpurun_out/pmc_f64/d_counter_collection.csv --bench-log LOG \
-        --out profiles/r02_k_mask_pose_f64.json
+        --out profiles/r06fin_f64.json
 
 The SQ_INSTS_VALU_*_F64 counters count wave-level instructions; one f64 instruction of a 64-lane
 wave is 64 lane operations, an FMA counting 2 FLOPs.  Lanes masked off by exec are counted as

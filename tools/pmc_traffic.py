@@ -7,7 +7,7 @@ hold both), on a serial bench command (one stream, so every launch is that kerne
     rocprofv3 --pmc WRITE_SIZE --output-format csv -d rocprof_out/pmc_write -o w -- python bench.py --full --no-cpu-baseline --serial ...
     python tools/pmc_traffic.py rocprof_out/pmc_fetch/f_counter_collection.csv \
         rocprof_out/pmc_write/w_counter_collection.csv --bench-log rocprof_out/pmc_fetch.log \
-        --out profiles/r02_traffic.json
+        --out profiles/r06fin_traffic.json
 
 Units and corrections (/opt/skills/guides/MI355X_MICROARCH.md, "HBM [CDNA4]"): FETCH_SIZE and
 WRITE_SIZE are KiB; on gfx950 FETCH_SIZE tallies wide coalesced streaming reads at half their
@@ -21,8 +21,8 @@ import csv
 import json
 from collections import defaultdict
 
-KERNELS = ("k_mask_pose_f64", "k_mask_pose", "k_feat_wave_reg", "k_feat_wave_run", "k_feat_chunk_reg", "k_feat_chunk_flagged", "k_feat_chunk", "k_feat_select", "k_bin_count", "k_bin_scan", "k_bin_curv", "k_select",
-           "k_plane_table_sorted", "k_associate_strips", "k_associate_lds", "k_associate_sorted", "k_solve")
+KERNELS = ("k_mask_pose_f64", "k_mask_pose", "k_feat_wave_reg", "k_feat_wave_run", "k_feat_chunk_flagged", "k_feat_chunk", "k_feat_select", "k_bin_count", "k_bin_scan", "k_bin_curv", "k_select",
+           "k_plane_table_sorted", "k_associate_strips", "k_solve")
 
 
 def launches(path):
