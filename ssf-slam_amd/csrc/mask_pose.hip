@@ -377,14 +377,16 @@ SSF_DEV void for_points_deep(const Ts* __restrict__ P, const Ts* __restrict__ Fl
     }
 }
 
-// EM: two points per step (i, i + T) so every parameter read serves both.  The second point of
-// the last step may not exist (w1 = 0: computed on a duplicate, weighted out).  Loads clamped
-// and unconditional, as in for_points; the next step's pair is held in registers.  Two register
+// EM: two points per step (i, i + T) so every parameter read serves both: fn2(xa, xb) for every
+// full pair, then fn1(xa) for a thread's lone last point (its second point does not exist), so
+// the pair body carries no weight for a missing point.  Loads clamped and unconditional, as in
+// for_points; the next step's pair is held in registers.  Two register
 // pairs in flight, or the loop unrolled with swapping register sets, were 6 % / 4 % slower (the
 // compiler waits for the loads right after issuing them, r6t / r6u); DESIGN 6.1 lists the other
 // forms that were measured and not kept.
-template <class Ts, class Fn>
-SSF_DEV void for_point_pairs(const Ts* __restrict__ P, const Ts* __restrict__ Fl, int64_t r0, int64_t r1, Fn&& fn) {
+template <class Ts, class Fn2, class Fn1>
+SSF_DEV void for_point_pairs(const Ts* __restrict__ P, const Ts* __restrict__ Fl, int64_t r0, int64_t r1, Fn2&& fn2,
+                             Fn1&& fn1) {
     // frames of at most 2^32 / (3 sizeof(Ts)) points (mask_pose_batch rejects larger ones)
     const Ts* Pb = P + 3 * r0;
     const Ts* Fb = Fl + 3 * r0;
@@ -396,14 +398,19 @@ SSF_DEV void for_point_pairs(const Ts* __restrict__ P, const Ts* __restrict__ Fl
     auto load = [&](uint32_t k, Ts r[6]) { load3_off(Fb, k * S, r); load3_off(Pb, k * S, r + 3); };
     load(i, ra);
     load(min(i + T, last), rb);
-    for (; i < n; i += 2 * T) {
+    for (; i + T < n; i += 2 * T) {
         double xa[6], xb[6];
 #pragma unroll
         for (int d = 0; d < 6; ++d) { xa[d] = (double)ra[d]; xb[d] = (double)rb[d]; }
-        const double wb = (i + T < n) ? 1.0 : 0.0;
         load(min(i + 2 * T, last), ra);
         load(min(i + 3 * T, last), rb);
-        fn(xa, xb, wb);
+        fn2(xa, xb);
+    }
+    if (i < n) {                                       // ra holds point i
+        double xa[6];
+#pragma unroll
+        for (int d = 0; d < 6; ++d) xa[d] = (double)ra[d];
+        fn1(xa);
     }
 }
 
@@ -1332,48 +1339,64 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
 #pragma unroll
         for (int k = 0; k < 29; ++k) acc[k] = 0.0;
         // sum of log1p(e) over the thread's points = log of the product of (1 + e), kept as
-        // mantissa * 2^pexp (frexp per point: the product never overflows, one log per thread)
+        // mantissa * 2^pexp (frexp per pair: the product never overflows, one log per thread)
         double prod = 1.0;
         int pexp = 0;
 #ifdef SSF_MASK_STAMPS
         if (it == 1 && tid == 0) S.dg_e[0] = S.dg_e[1] = S.dg_e[2] = 0.0;
         const unsigned long long e_t0 = __builtin_amdgcn_s_memtime();
 #endif
-        // the laundered LDS bases outside the loop: two loop-invariant VGPRs.  Laundered per
+        // the laundered LDS bases outside the loop: two loop-invariant VGPRs (the parameter
+        // reads themselves stay in the loop, see the pair body).  Laundered per
         // pair, their constants were rematerialised every iteration into registers the
         // prefetched point loads had landed in, so the loads were copied away (and waited for)
         // right after they were issued
         const LdsDouble* AqL = lds_laundered(S.Aq);
         const LdsDouble* bqL = lds_laundered(S.bq);
-        for_point_pairs(P, Fl, r0, r1, [&](const double* xa, const double* xb, double wb) {
-            const LdsDouble* Aq = AqL;
-            const LdsDouble* bq = bqL;
+        // one point's E-step from its delta and its M-step moments; returns d = 1 + e
+        auto em_point = [&](const double* v, double dl) {
+            const double e = exp(-fabs(dl));
+            const double d = 1.0 + e;
+            acc[28] += dl > 0.0 ? dl : 0.0;
+            const double inv = recip_1_2(d);
+            const double r = dl > 0.0 ? inv : e * inv;
+            acc[0] += r;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double rv = r * v[a];
+                acc[1 + a] += rv;
+#pragma unroll
+                for (int b = a; b < 6; ++b) acc[7 + up(a, b)] += rv * v[b];
+            }
+            return d;
+        };
+        // prod is in [0.5, 1) (1 at the start) and every d in (1, 2], so two factors stay below 4:
+        // one renormalisation per pair, and a power-of-two scale commutes with the rounding
+        auto renorm = [&]() {
+            pexp += __builtin_amdgcn_frexp_exp(prod);
+            prod = __builtin_amdgcn_frexp_mant(prod);
+        };
+        for_point_pairs(P, Fl, r0, r1, [&](const double* xa, const double* xb) {
             double va[6], vb[6];
 #pragma unroll
             for (int a = 0; a < 6; ++a) { va[a] = xa[a] - mean[a]; vb[a] = xb[a] - mean[a]; }
-            double dl[2];
-            em_delta2(va, vb, Aq, bq, cq, dl[0], dl[1]);
+            double da, db;
+            // the 27 parameters are read from LDS for every pair (the compiler may not keep them
+            // across this point).  Held in VGPRs for the pass, as before the lone-point body
+            // existed, they leave this loop short of registers: one parameter reloaded from
+            // scratch per pair and the prefetched loads waited for in the iteration that issues
+            // them (mask alone -5 %)
+            asm volatile("" ::: "memory");
+            em_delta2(va, vb, AqL, bqL, cq, da, db);
+            prod *= em_point(va, da);
+            prod *= em_point(vb, db);
+            renorm();
+        }, [&](const double* xa) {               // em_delta1: the operations of one half of em_delta2
+            double va[6];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const double* v = h ? vb : va;
-                const double wgt = h ? wb : 1.0;
-                const double e = exp(-fabs(dl[h]));
-                const double d = 1.0 + e;
-                acc[28] += wgt * (dl[h] > 0.0 ? dl[h] : 0.0);
-                prod *= (h ? (wb > 0.0 ? d : 1.0) : d);
-                pexp += __builtin_amdgcn_frexp_exp(prod);
-                prod = __builtin_amdgcn_frexp_mant(prod);
-                const double inv = recip_1_2(d);
-                const double r = wgt * (dl[h] > 0.0 ? inv : e * inv);
-                acc[0] += r;
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    const double rv = r * v[a];
-                    acc[1 + a] += rv;
-#pragma unroll
-                    for (int b = a; b < 6; ++b) acc[7 + up(a, b)] += rv * v[b];
-                }
-            }
+            for (int a = 0; a < 6; ++a) va[a] = xa[a] - mean[a];
+            prod *= em_point(va, em_delta1(va, AqL, bqL, cq));
+            renorm();
         });
         acc[28] += log(prod) + (double)pexp * 0.69314718055994530942;
         block_sum_rs<29>(acc, red);
