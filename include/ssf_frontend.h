@@ -477,6 +477,58 @@ int32_t ssf_icp_batch(ssf_ctx* ctx, void* stream, int32_t n_prob, const float* d
                       const int64_t* d_tgt_off, const int64_t* h_tgt_off,
                       const ssf_icp_params* params, const float* h_guess, double* h_out);
 
+/* ssf_pose_graph_batch replaces the pose graph of mapOptmization: the prior and odometry
+ * factors of addOdomFactor (src/mapOptmization.cpp:147-165), the loop factor (:274) and
+ * runOptimize (:280-293), as batched Gauss-Newton on SE(3) over n_graphs independent graphs,
+ * one work-group per graph, the iteration loop on the device.
+ *   d_pose        in/out, 7 doubles per node (q xyzw, t), the graphs' nodes at d_node_off /
+ *                 h_node_off (int32, n_graphs + 1)
+ *   d_edge_ij     int32 pairs (i, j), graph-local node indices, at d_edge_off / h_edge_off
+ *   d_edge_meas   7 doubles per edge: the measured Xi^-1 Xj
+ *   d_edge_var    6 variances per edge, tangent order rotation (3) then translation (3)
+ *   d_prior_pose, d_prior_var   the prior on node 0 of every graph (7 and 6 doubles per graph)
+ *   d_stats       n_graphs * SSF_PGO_OUT_STRIDE doubles (SSF_PGO_OUT_*), written for every graph
+ *   d_cost_log    nullable; n_graphs * (max_iter + 1) doubles: the cost at every linearisation
+ *                 and after the last step, NaN beyond
+ * Retraction X * [Exp(w), v]; residual [Log(R_E); t_E] of E = Z^-1 Xi^-1 Xj whitened by the
+ * standard deviations.  Stops when |cost_{k-1} - cost_k| <= func_tol * cost_{k-1} (func_tol 0:
+ * exactly max_iter steps); steps are never rejected.  Edges with |i - j| == 1 and the prior form
+ * the block-tridiagonal part; every other edge is a loop edge, at most SSF_PGO_MAX_LOOPS per
+ * graph.  A graph that ends with SSF_PGO_EMPTY, _BAD_INPUT, _TOO_MANY_LOOPS or _NOT_PD keeps its
+ * poses bit for bit and does not affect the other graphs.  Asynchronous on stream.  SSF_E_ARG
+ * (before any HIP call) on a null context or pointer, a negative count, max_iter outside
+ * [0, SSF_PGO_MAX_ITER] or host offsets that do not start at 0 or decrease. */
+typedef struct {
+    int32_t max_iter;       /* 8: the isam->update calls of a loop closure (:281-288)  */
+    double func_tol;        /* 1e-6: the front-end's Ceres function tolerance          */
+} ssf_pgo_params;
+#define SSF_PGO_MAX_LOOPS 32
+#define SSF_PGO_MAX_ITER 1024
+#define SSF_PGO_OUT_STRIDE 8
+enum {
+    SSF_PGO_OUT_STATUS = 0, SSF_PGO_OUT_ITERATIONS = 1, SSF_PGO_OUT_COST0 = 2, SSF_PGO_OUT_COST = 3,
+    SSF_PGO_OUT_DX = 4,     /* max-norm of the last step */
+    SSF_PGO_OUT_LOOPS = 5
+};
+enum {
+    SSF_PGO_OK = 0,               /* stopped at max_iter                                       */
+    SSF_PGO_CONVERGED = 1,        /* stopped by func_tol                                       */
+    SSF_PGO_EMPTY = 2,            /* no nodes                                                  */
+    SSF_PGO_BAD_INPUT = 3,        /* edge index outside [0, K), i == j, non-finite pose or
+                                     measurement, zero quaternion, variance non-finite or <= 0 */
+    SSF_PGO_TOO_MANY_LOOPS = 4,   /* more loop edges than SSF_PGO_MAX_LOOPS                    */
+    SSF_PGO_NOT_PD = 5            /* Cholesky pivot <= 0 (e.g. a chain link without an edge) or
+                                     a non-finite step                                         */
+};
+int32_t ssf_pgo_params_default(ssf_pgo_params* out);
+int32_t ssf_pose_graph_batch(ssf_ctx* ctx, void* stream, int32_t n_graphs, double* d_pose,
+                             const int32_t* d_node_off, const int32_t* h_node_off,
+                             const int32_t* d_edge_ij, const double* d_edge_meas,
+                             const double* d_edge_var, const int32_t* d_edge_off,
+                             const int32_t* h_edge_off, const double* d_prior_pose,
+                             const double* d_prior_var, const ssf_pgo_params* params,
+                             double* d_stats, double* d_cost_log);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libssf_frontend.so")
 SYNTH_LIB = os.path.join(OUT_DIR, "libssf_synth.so")
 SOURCES = ["abi.hip", "features.hip", "registration.hip", "mask_pose.hip", "mask_pose_f64.hip", "kabsch_f32.hip",
-           "loop.hip", "pointnet2.hip"]
+           "loop.hip", "pose_graph.hip", "pointnet2.hip"]
 # sources that include another source file
 SRC_DEPS = {"mask_pose_f64.hip": ["mask_pose.hip"]}
 HEADERS = ["ssf_device.hpp", "ssf_internal.hpp", "svd3.hpp", os.path.join("..", "..", "include", "ssf_frontend.h"),
@@ -25,7 +25,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall"]
 # The f64 GMM/Kabsch kernel is compared with tolerances (labels, iteration counts, 1e-5 m), not
 # bit for bit, so it may contract multiply-adds into FMAs (half the f64 instructions).
-FILE_FLAGS = {"mask_pose.hip": ["-ffp-contract=fast"], "mask_pose_f64.hip": ["-ffp-contract=fast"]}
+# The pose-graph solver is f64 linear algebra checked against a numpy solver with tolerances.
+FILE_FLAGS = {"mask_pose.hip": ["-ffp-contract=fast"], "mask_pose_f64.hip": ["-ffp-contract=fast"],
+              "pose_graph.hip": ["-ffp-contract=fast"]}
 
 
 def _stale(target, deps):

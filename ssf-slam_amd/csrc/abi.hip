@@ -83,6 +83,10 @@ struct ssf_ctx {
     // loop closure (loop.hip): voxel-grid sort scratch; ICP transformed source, 1-NN keys,
     // per-problem state and guesses
     DevBuf vg, icp_cur, icp_key, icp_st, icp_guess;
+    // pose graph (pose_graph.hip): per-graph descriptors (host copy reused across calls) and the
+    // working poses, factor records, block factors and right-hand sides of every graph
+    DevBuf pgo_desc, pgo_scratch;
+    std::vector<ssf::PgoGraph> pgo_h;
     // host RandomState (MT19937, numpy legacy seeding)
     uint32_t mt[624];
     int mt_pos = 625;
@@ -232,7 +236,8 @@ void ssf_destroy(ssf_ctx* c) {
     (void)hipSetDevice(c->device);
     DevBuf* bufs[] = {&c->rid, &c->hist, &c->ring_off, &c->ring_xyzi, &c->sel, &c->sel_cnt, &c->fix,
                       &c->plane1, &c->off1, &c->cnt1, &c->corr, &c->cidx, &c->pair, &c->start1, &c->vg,
-                      &c->icp_cur, &c->icp_key, &c->icp_st, &c->icp_guess, &c->esel,
+                      &c->icp_cur, &c->icp_key, &c->icp_st, &c->icp_guess, &c->pgo_desc,
+                      &c->pgo_scratch, &c->esel,
                       &c->ecorr, &c->fcnt, &c->fidx, &c->fbits, &c->fcurv, &c->rtab, &c->firr, &c->flmap};
     for (auto& ds : c->dslot) {
         if (ds.used) { (void)hipEventSynchronize(ds.used); (void)hipEventDestroy(ds.used); }
@@ -988,6 +993,58 @@ int32_t ssf_icp_batch(ssf_ctx* c, void* stream, int32_t n_prob, const float* d_s
         o[SSF_ICP_OUT_STATE] = hs[k].state;
         o[SSF_ICP_OUT_NCORR] = hs[k].n_corr;
     }
+    return SSF_OK;
+}
+
+int32_t ssf_pgo_params_default(ssf_pgo_params* out) {
+    if (!out) return SSF_E_ARG;
+    out->max_iter = 8;              // mapOptmization.cpp:281-288: isam->update calls of a loop closure
+    out->func_tol = 1e-6;           // the front-end's Ceres function tolerance
+    return SSF_OK;
+}
+
+int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
+                             const int32_t* d_node_off, const int32_t* h_node_off,
+                             const int32_t* d_edge_ij, const double* d_edge_meas,
+                             const double* d_edge_var, const int32_t* d_edge_off,
+                             const int32_t* h_edge_off, const double* d_prior_pose,
+                             const double* d_prior_var, const ssf_pgo_params* prm,
+                             double* d_stats, double* d_cost_log) {
+    if (!c) return SSF_E_ARG;
+    if (n_graphs < 0 || !prm || prm->max_iter < 0 || prm->max_iter > SSF_PGO_MAX_ITER ||
+        !(prm->func_tol >= 0.0) ||
+        (n_graphs > 0 && (!d_pose || !d_node_off || !h_node_off || !d_edge_ij || !d_edge_meas || !d_edge_var ||
+                          !d_edge_off || !h_edge_off || !d_prior_pose || !d_prior_var || !d_stats)))
+        return fail(c, SSF_E_ARG, "pose_graph_batch: bad arguments");
+    if (n_graphs == 0) return SSF_OK;
+    if (h_node_off[0] != 0 || h_edge_off[0] != 0)
+        return fail(c, SSF_E_ARG, "pose_graph_batch: offsets must start at 0");
+    for (int g = 0; g < n_graphs; ++g)
+        if (h_node_off[g + 1] < h_node_off[g] || h_edge_off[g + 1] < h_edge_off[g])
+            return fail(c, SSF_E_ARG, "pose_graph_batch: offsets not monotone");
+    c->pgo_h.resize((size_t)n_graphs);
+    size_t total = 0;
+    for (int g = 0; g < n_graphs; ++g) {
+        ssf::PgoGraph& G = c->pgo_h[(size_t)g];
+        G.node0 = h_node_off[g]; G.K = h_node_off[g + 1] - h_node_off[g];
+        G.edge0 = h_edge_off[g]; G.E = h_edge_off[g + 1] - h_edge_off[g];
+        G.lcap = std::min(std::max(G.E - (G.K - 1), 0), SSF_PGO_MAX_LOOPS);
+        G.pad = 0;
+        G.scratch_off = (int64_t)total;
+        total += ssf::pgo_graph_doubles(G.K, G.E, G.lcap);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(c, stream);
+    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    SSF_TRY_HIP(c, c->pgo_desc.ensure(sizeof(ssf::PgoGraph) * (size_t)n_graphs), "alloc pose-graph descriptors");
+    SSF_TRY_HIP(c, c->pgo_scratch.ensure(sizeof(double) * total), "alloc pose-graph scratch");
+    SSF_TRY_HIP(c, hipMemcpyAsync(c->pgo_desc.p, c->pgo_h.data(), sizeof(ssf::PgoGraph) * (size_t)n_graphs,
+                                  hipMemcpyHostToDevice, s), "H2D pose-graph descriptors");
+    hipError_t e = ssf::launch_pose_graph(s, n_graphs, c->pgo_desc.as<ssf::PgoGraph>(), d_pose, d_node_off,
+                                          d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
+                                          d_prior_var, prm->max_iter, prm->func_tol,
+                                          c->pgo_scratch.as<double>(), d_stats, d_cost_log);
+    if (e != hipSuccess) return hip_fail(c, e, "pose_graph launch");
     return SSF_OK;
 }
 

@@ -203,4 +203,18 @@ hipError_t launch_icp_fitness(hipStream_t s, int n_prob, const float4* src, cons
                               const int64_t* toff, int64_t max_nt, IcpState* st,
                               unsigned long long* key);
 
+// ---- launcher (pose_graph.hip) ----
+struct PgoGraph {             // one per graph, built on the host from the host offsets
+    int64_t scratch_off;      // this graph's piece of the context scratch, in doubles
+    int32_t node0, K, edge0, E;
+    int32_t lcap;             // min(max(E - (K - 1), 0), SSF_PGO_MAX_LOOPS): loop edges it has room for
+    int32_t pad;
+};
+size_t pgo_graph_doubles(int K, int E, int lcap);
+hipError_t launch_pose_graph(hipStream_t s, int n_graphs, const PgoGraph* desc, double* pose,
+                             const int32_t* node_off, const int32_t* edge_ij, const double* edge_meas,
+                             const double* edge_var, const int32_t* edge_off, const double* prior_pose,
+                             const double* prior_var, int max_iter, double func_tol, double* scratch,
+                             double* stats, double* cost_log);
+
 }  // namespace ssf

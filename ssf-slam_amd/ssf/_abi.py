@@ -39,7 +39,7 @@ EXPORTS = [
     "ssf_profile_read", "ssf_set_mask_split", "ssf_mask_pose_batch_f64",
     "ssf_edge_config_default", "ssf_set_edge_config", "ssf_extract_features_batch",
     "ssf_edge_table_batch", "ssf_register_batch_edges", "ssf_kabsch_f32_batch",
-    "ssf_set_mask_schedule", "ssf_register_plan",
+    "ssf_set_mask_schedule", "ssf_register_plan", "ssf_pgo_params_default", "ssf_pose_graph_batch",
 ]
 # Every symbol include/ssf_pointnet2.h declares (TFlow point-set operators).
 PN2_EXPORTS = [
@@ -53,6 +53,16 @@ ICP_OUT_STRIDE = 24
 ICP_OUT = dict(T=0, FITNESS=16, CONVERGED=17, ITERATIONS=18, STATE=19, NCORR=20)
 ICP_STATES = {0: "not_converged", 1: "iterations", 2: "transform", 3: "abs_mse", 4: "rel_mse",
               5: "no_correspondences"}
+
+
+PGO_MAX_LOOPS, PGO_MAX_ITER, PGO_OUT_STRIDE = 32, 1024, 8
+PGO_OUT = dict(STATUS=0, ITERATIONS=1, COST0=2, COST=3, DX=4, LOOPS=5)
+PGO_OK, PGO_CONVERGED, PGO_EMPTY, PGO_BAD_INPUT, PGO_TOO_MANY_LOOPS, PGO_NOT_PD = range(6)
+PGO_STATUS = {0: "ok", 1: "converged", 2: "empty", 3: "bad_input", 4: "too_many_loops", 5: "not_pd"}
+
+
+class PgoParams(C.Structure):
+    _fields_ = [("max_iter", C.c_int32), ("func_tol", C.c_double)]
 
 
 class IcpParams(C.Structure):
@@ -176,6 +186,10 @@ def lib():
     L.ssf_icp_params_default.restype = i32
     L.ssf_icp_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(IcpParams), vp, vp]
     L.ssf_icp_batch.restype = i32
+    L.ssf_pgo_params_default.argtypes = [C.POINTER(PgoParams)]
+    L.ssf_pgo_params_default.restype = i32
+    L.ssf_pose_graph_batch.argtypes = [vp, vp, i32] + [vp] * 10 + [C.POINTER(PgoParams), vp, vp]
+    L.ssf_pose_graph_batch.restype = i32
     L.ssf_pn2_last_error.argtypes = []
     L.ssf_pn2_last_error.restype = C.c_char_p
     L.ssf_pn2_furthest_point_sample.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]

@@ -7,8 +7,11 @@ keyframe / loop-detection / local-map logic around them (isKeyFrame :129-144,
 addPose3D6D :78-107, detectLoopFrameID :167-197, getLoopLocalMap :200-218, addLoopFactor
 :221-272, trans_loop_adjust :325, the T_map_0_curr chain :447-450) and emits the loop
 constraint the reference adds to its GTSAM graph (BetweenFactor poseFrom.between(poseTo),
-noise = the ICP fitness score).  GTSAM iSAM2 is not part of this path (absent from the image):
-the published pose is the loop-adjusted odometry, see DESIGN.md.
+noise = the ICP fitness score).  By default the published pose is the loop-adjusted odometry;
+``LoopCloser(optimize=True)`` also records the factors of addOdomFactor (:147-165), optimises
+the pose graph on the GPU at every loop closure (``optimize_pose_graphs`` <- runOptimize
+:280-293, batched Gauss-Newton in pose_graph.hip, not GTSAM's iSAM2) and rewrites every
+keyframe pose (correctPoses :296-332), see DESIGN.md §6.7.
 
 Pose helpers restate pcl/common/eigen.h: getTransformation (roll/pitch/yaw -> affine,
 yaw * pitch * roll) and getTranslationAndEulerAngles.  Key poses are stored in float, as the
@@ -121,6 +124,86 @@ def icp(fe: Frontend, src: torch.Tensor, tgt: torch.Tensor, params=None, guess=N
                      ht, params, None if guess is None else [guess])[0]
 
 
+def pgo_params(max_iter=8, func_tol=1e-6):
+    p = _abi.PgoParams()
+    _abi.lib().ssf_pgo_params_default(C.byref(p))
+    p.max_iter, p.func_tol = int(max_iter), float(func_tol)
+    return p
+
+
+def optimize_pose_graphs(fe: Frontend, graphs, params=None):
+    """Batched pose-graph optimisation, one launch for every graph of the list.  A graph is a
+    dict(poses [K, 7] f64 (q xyzw, t), edge_ij [E, 2] graph-local, edge_meas [E, 7], edge_var
+    [E, 6] (rotation then translation), prior_pose [7], prior_var [6] on node 0).
+    -> list of dict(poses [K, 7], status (PGO_*), status_name, iterations, cost0, cost, dx, loops,
+    cost_log).  A graph whose status is not ok / converged gets its poses back unchanged."""
+    G = len(graphs)
+    if G == 0:
+        return []
+    params = params or pgo_params()
+    f64 = lambda key, w: [np.ascontiguousarray(g[key], np.float64).reshape(-1, w) for g in graphs]  # noqa: E731
+    poses, meas, var = f64("poses", 7), f64("edge_meas", 7), f64("edge_var", 6)
+    ij = [np.ascontiguousarray(g["edge_ij"], np.int32).reshape(-1, 2) for g in graphs]
+    for k in range(G):
+        if not (len(ij[k]) == len(meas[k]) == len(var[k])):
+            raise ValueError(f"graph {k}: edge_ij, edge_meas and edge_var differ in length")
+    prior = np.concatenate(f64("prior_pose", 7))
+    pvar = np.concatenate(f64("prior_var", 6))
+    if prior.shape != (G, 7) or pvar.shape != (G, 6):
+        raise ValueError("prior_pose is 7 and prior_var 6 doubles per graph")
+    h_noff = torch.tensor(np.concatenate([[0], np.cumsum([len(p) for p in poses])]), dtype=torch.int32)
+    h_eoff = torch.tensor(np.concatenate([[0], np.cumsum([len(e) for e in ij])]), dtype=torch.int32)
+    dev = fe.device
+
+    def up(parts, dtype, width):                  # never a null pointer, even with nothing in it
+        a = np.concatenate(parts + [np.zeros((1, width), dtype)])
+        return torch.from_numpy(a).to(dev)
+
+    d_pose, d_meas, d_var = up(poses, np.float64, 7), up(meas, np.float64, 7), up(var, np.float64, 6)
+    d_ij = up(ij, np.int32, 2)
+    d_prior, d_pvar = torch.from_numpy(prior).to(dev), torch.from_numpy(pvar).to(dev)
+    d_noff, d_eoff = h_noff.to(dev), h_eoff.to(dev)
+    stats = torch.zeros(G, _abi.PGO_OUT_STRIDE, dtype=torch.float64, device=dev)
+    clog = torch.zeros(G, params.max_iter + 1, dtype=torch.float64, device=dev)
+    fe._check(_abi.lib().ssf_pose_graph_batch(
+        fe._h, _stream(dev), G, _ptr(d_pose), _ptr(d_noff), C.c_void_p(h_noff.data_ptr()), _ptr(d_ij),
+        _ptr(d_meas), _ptr(d_var), _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(d_prior), _ptr(d_pvar),
+        C.byref(params), _ptr(stats), _ptr(clog)), "ssf_pose_graph_batch")
+    out_pose, st, cl = d_pose.cpu().numpy(), stats.cpu().numpy(), clog.cpu().numpy()
+    res = []
+    for k in range(G):
+        o = st[k]
+        status = int(o[_abi.PGO_OUT["STATUS"]])
+        res.append(dict(poses=out_pose[int(h_noff[k]):int(h_noff[k + 1])].copy(), status=status,
+                        status_name=_abi.PGO_STATUS.get(status, "?"),
+                        iterations=int(o[_abi.PGO_OUT["ITERATIONS"]]), cost0=float(o[_abi.PGO_OUT["COST0"]]),
+                        cost=float(o[_abi.PGO_OUT["COST"]]), dx=float(o[_abi.PGO_OUT["DX"]]),
+                        loops=int(o[_abi.PGO_OUT["LOOPS"]]),
+                        cost_log=[float(v) for v in cl[k] if not math.isnan(v)]))
+    return res
+
+
+def pose7_from_matrix(T):
+    """4x4 -> (q xyzw, t), 7 doubles (the largest-component branch of the usual conversion)."""
+    R = np.asarray(T, np.float64)[:3, :3]
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = math.sqrt(tr + 1.0) * 2
+        q = [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, 0.25 * s]
+    else:
+        i = int(np.argmax([R[0, 0], R[1, 1], R[2, 2]]))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = math.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0) * 2
+        q = [0.0, 0.0, 0.0, (R[k, j] - R[j, k]) / s]
+        q[i], q[j], q[k] = 0.25 * s, (R[j, i] + R[i, j]) / s, (R[k, i] + R[i, k]) / s
+    q = np.asarray(q, np.float64)
+    return np.concatenate([q / np.linalg.norm(q), np.asarray(T, np.float64)[:3, 3]])
+
+
+PRIOR_VARIANCES = (1e-2, 1e-2, math.pi * math.pi, 1e8, 1e8, 1e8)      # priorNoise (:151)
+ODOM_VARIANCES = (1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4)                  # odometryNoise (:160)
+
+
 def transform_cloud(xyzi: torch.Tensor, T) -> torch.Tensor:
     """pcl::transformPointCloud with an Affine3d: double arithmetic, float result, intensity
     kept."""
@@ -155,6 +238,13 @@ class LoopCloser:
     loop_record_index: int = 0
     trans_loop_adjust: np.ndarray = field(default_factory=lambda: np.eye(4))
     constraints: list = field(default_factory=list)
+    # optimize=True: the pose graph the reference keeps in GTSAM (addOdomFactor :147-165, the loop
+    # factor :274), solved on the GPU at every loop closure
+    optimize: bool = False
+    graph_init: list = field(default_factory=list)     # per keyframe: the estimate, 7 doubles
+    graph_edges: list = field(default_factory=list)    # (i, j, measurement 7 doubles, 6 variances)
+    graph_prior: np.ndarray | None = None
+    last_optimization: dict | None = None
 
     def _T6(self, i):
         p = self.key6d[i]
@@ -221,6 +311,39 @@ class LoopCloser:
         self.constraints.append(c)
         return c
 
+    # ---- pose graph (optimize=True)
+    def _add_odom_factor(self, arr6d):
+        """addOdomFactor (:147-165): currPose from the double arr6d, lastPose from the stored
+        float key pose."""
+        curr = get_transformation(*arr6d)
+        n = len(self.key6d)
+        if n == 1:
+            self.graph_prior = pose7_from_matrix(curr)
+        else:
+            self.graph_edges.append((n - 2, n - 1, pose7_from_matrix(between(self._T6(n - 2), curr)),
+                                     ODOM_VARIANCES))
+        self.graph_init.append(pose7_from_matrix(curr))
+
+    def pose_graph(self):
+        """The recorded graph in the form optimize_pose_graphs takes."""
+        return dict(poses=np.array(self.graph_init, np.float64).reshape(-1, 7),
+                    edge_ij=np.array([(e[0], e[1]) for e in self.graph_edges], np.int32).reshape(-1, 2),
+                    edge_meas=np.array([e[2] for e in self.graph_edges], np.float64).reshape(-1, 7),
+                    edge_var=np.array([e[3] for e in self.graph_edges], np.float64).reshape(-1, 6),
+                    prior_pose=np.asarray(self.graph_prior, np.float64), prior_var=np.array(PRIOR_VARIANCES))
+
+    def apply_optimization(self, res):
+        """correctPoses (:315-332) with a solution of pose_graph(): every key pose rewritten,
+        rounded to float as PointXYZIRPYT stores it.  -> T_map_0_curr rebuilt from the last one."""
+        if res["status"] not in (_abi.PGO_OK, _abi.PGO_CONVERGED):
+            raise _abi.SSFError(f"pose-graph optimisation failed: {res['status_name']}")
+        self.last_optimization = res
+        for i, p in enumerate(res["poses"]):
+            six = get_translation_and_euler_angles(pose_from_quat(p[:4], p[4:]))
+            self.key6d[i][:6] = np.array(six, np.float32).tolist()
+            self.graph_init[i] = np.array(p, np.float64)
+        return self._T6(-1)
+
     def process(self, plane_xyzi: torch.Tensor, q_xyzw, t, stamp: float):
         """One synchronised (/plane_frame_cloud2, /frame_odom2) pair (cloudThread :429-451 +
         mapOptimization :455-467).  Returns (T_map_0_curr, constraint or None, is_key)."""
@@ -230,7 +353,31 @@ class LoopCloser:
         x, y, z, r, p, yw = get_translation_and_euler_angles(T)
         self.key6d.append(np.array([x, y, z, r, p, yw], np.float32).tolist() + [float(stamp)])
         self.key_frames.append(plane_xyzi.contiguous())
+        if self.optimize:
+            self._add_odom_factor((x, y, z, r, p, yw))
         c = self.add_loop_factor()
         if c is not None:                                   # correctPoses (:321-326)
+            if self.optimize:
+                T = self.close_loop(c)
             self.trans_loop_adjust = self.trans_loop_adjust @ c.correction
         return T, c, True
+
+    def add_loop_edge(self, c: LoopConstraint):
+        """The loop factor of :263-274: cur -> pre, poseFrom.between(poseTo), the fitness as all
+        six variances."""
+        self.graph_edges.append((c.key_cur, c.key_pre, pose7_from_matrix(c.between), (float(c.noise),) * 6))
+
+    def close_loop(self, c: LoopConstraint):
+        """runOptimize + correctPoses for one closed loop -> the corrected T_map_0_curr."""
+        self.add_loop_edge(c)
+        return self.apply_optimization(optimize_pose_graphs(self.fe, [self.pose_graph()])[0])
+
+
+def optimize_loop_closers(fe: Frontend, closers, constraints, params=None):
+    """Several sequences that closed a loop in the same step, solved in one launch: adds each
+    constraint to its closer's graph, optimises all graphs together and applies correctPoses to
+    each.  -> the corrected T_map_0_curr of every closer."""
+    for lc, c in zip(closers, constraints):
+        lc.add_loop_edge(c)
+    res = optimize_pose_graphs(fe, [lc.pose_graph() for lc in closers], params)
+    return [lc.apply_optimization(r) for lc, r in zip(closers, res)]

@@ -252,14 +252,18 @@ class MapOptimizationNode:
     /map_laser_path_res3, and appends TUM lines to RESULT_PATH (:355-374).  GTSAM iSAM2 is not
     part of this path: the published pose is the loop-adjusted odometry trans_loop_adjust *
     T_fodom_0_curr (:450) at every frame (the reference publishes its iSAM2 estimate for
-    keyframes only), and the loop constraints are kept in ``closer.constraints``."""
+    keyframes only), and the loop constraints are kept in ``closer.constraints``.
+    optimize=True: a loop closure also optimises the pose graph on the GPU and rewrites every
+    keyframe pose (runOptimize / correctPoses, :280-332; ``closer.key6d``,
+    ``closer.last_optimization``); the keyframe that closed the loop is published at its
+    corrected pose."""
 
     def __init__(self, publish, device=None, frontend: Frontend | None = None,
-                 tum_path: str | None = None):
+                 tum_path: str | None = None, optimize: bool = False):
         from .loop import LoopCloser, get_translation_and_euler_angles  # noqa: F401
         self.publish = publish
         self.fe = frontend or Frontend(64, device=device)
-        self.closer = LoopCloser(self.fe)
+        self.closer = LoopCloser(self.fe, optimize=True) if optimize else LoopCloser(self.fe)
         self.planes, self.odoms = [], []          # planeQueue / odometryQueue (:65-75)
         self.path = Path()
         self.writer = sio.TumWriter(tum_path) if tum_path else None
@@ -309,17 +313,19 @@ LAUNCH_GRAPHS = {
 def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, device=None,
                  solver: str = "ceres_lm", max_iter: int | None = None, seed: int | None = None,
                  rate_hz: float = 10.0, launch: str = "onlyPC", map_tum_path: str | None = None,
-                 truncate_results: bool = False):
+                 truncate_results: bool = False, map_optimize: bool = False):
     """Replay a DATASET_PATH directory through the node graph of launch/run_<launch>.launch:
       onlyPC: PointCloudOdometry_onlyPC -> frameFeature -> lidarOdometry_onlyPC (registration)
       noSeg:  PointCloudOdometry_noSeg (GMM mask + Kabsch -> /frame_odom1) -> frameFeature ->
               lidarOdometry (pose ingest + accumulation)
       Seg:    PointCloudOdometry (ground-truth mask s_fg_mask == 0) -> same as noSeg
-    plus mapOptmization when `map_tum_path` is given.  Stamps are synthetic and monotone (frame k
+    plus mapOptmization when `map_tum_path` is given (map_optimize: with the GPU pose-graph
+    optimisation of its loop closures).  Stamps are synthetic and monotone (frame k
     at k / rate_hz; the reference uses wall-clock ros::Time::now()).  The /frame_odom2 poses are
     appended to `tum_path` as TUM lines (like the reference, an existing file is extended unless
     truncate_results=True).
-    -> dict(odom1 [F, 7] f64 [t, q] (empty for onlyPC), odom2 [F-1, 7] f64 [t, q], stamps)"""
+    -> dict(odom1 [F, 7] f64 [t, q] (empty for onlyPC), odom2 [F-1, 7] f64 [t, q], stamps, loops;
+    with map_optimize also optimization (the last solve) and key_poses)"""
     if launch not in LAUNCH_GRAPHS:
         raise ValueError(f"launch {launch!r}: one of {sorted(LAUNCH_GRAPHS)}")
     src_mode, odo_kind, keys = LAUNCH_GRAPHS[launch]
@@ -354,7 +360,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
     if map_tum_path is not None:                     # mapOptmization on /plane_frame_cloud2 + /frame_odom2
         if map_tum_path and truncate_results:
             open(map_tum_path, "w").close()
-        mo = MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None)
+        mo = (MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None, optimize=True)
+              if map_optimize else MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None))
         bus.subscribe("/plane_frame_cloud2", mo.on_plane_cloud)
         bus.subscribe("/frame_odom2", mo.on_odom)
     period_ns = int(round(1e9 / rate_hz))
@@ -364,6 +371,10 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
         stamps.append(stamp)
         pco.on_frame(fr["pos1"], fr.get("gt"), stamp,
                      gt_mask=fr.get("s_fg_mask") if src_mode == "gt" else None)
-    return dict(odom1=np.asarray(odom1, np.float64).reshape(-1, 7),
-                odom2=np.asarray(odom2, np.float64).reshape(-1, 7), stamps=stamps,
-                loops=mo.closer.constraints if mo else [])
+    res = dict(odom1=np.asarray(odom1, np.float64).reshape(-1, 7),
+               odom2=np.asarray(odom2, np.float64).reshape(-1, 7), stamps=stamps,
+               loops=mo.closer.constraints if mo else [])
+    if map_optimize:                                 # the last solve (None: no loop was closed)
+        res["optimization"] = mo.closer.last_optimization if mo else None
+        res["key_poses"] = [list(k) for k in mo.closer.key6d] if mo else []
+    return res

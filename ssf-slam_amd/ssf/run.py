@@ -25,6 +25,11 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--map-tum", default=None,
                     help="also run mapOptmization (loop closure) and write its RESULT_PATH TUM file")
+    ap.add_argument("--map-optimize", action="store_true",
+                    help="with --map-tum: optimise the pose graph on a loop closure and rewrite the "
+                         "keyframe poses (runOptimize / correctPoses)")
+    ap.add_argument("--rate-hz", type=float, default=10.0,
+                    help="frame rate of the synthetic stamps (frame k at k / rate)")
     a = ap.parse_args(argv)
     from .nodes import run_sequence
     import os
@@ -34,14 +39,19 @@ def main(argv=None):
               f"--truncate starts a new file", file=sys.stderr)
     torch.cuda.set_device(a.device)
     res = run_sequence(a.dataset_path, a.tum, n_rows=a.rows, solver=a.solver, max_iter=a.iters,
-                       seed=a.seed, launch=a.launch, map_tum_path=a.map_tum,
-                       truncate_results=a.truncate)
+                       seed=a.seed, launch=a.launch, map_tum_path=a.map_tum, map_optimize=a.map_optimize,
+                       truncate_results=a.truncate, rate_hz=a.rate_hz)
+    extra = {}
+    if a.map_optimize:
+        opt = res["optimization"]
+        extra = {"map_optimize": None if opt is None else
+                 {k: opt[k] for k in ("status_name", "iterations", "cost0", "cost", "loops")}}
     print(json.dumps({"launch": a.launch, "tum": a.tum, "tum_mode": "truncate" if a.truncate else "append",
                       "frames": len(res["stamps"]),
                       "odom1_poses": int(res["odom1"].shape[0]),
                       "odom2_poses": int(res["odom2"].shape[0]),
                       "final_t": res["odom2"][-1, 0:3].tolist() if len(res["odom2"]) else None,
-                      "loops": len(res["loops"])}))
+                      "loops": len(res["loops"]), **extra}))
 
 
 if __name__ == "__main__":
