@@ -448,6 +448,26 @@ int32_t ssf_voxel_grid_batch(ssf_ctx* ctx, void* stream, int32_t n_clouds, const
                              const int64_t* d_off, const int64_t* h_off, float leaf,
                              float* d_out, int32_t* d_out_count);
 
+/* ssf_transform_clouds_batch replaces pcl::transformPointCloud(cloud, out, Eigen::Affine3d) as
+ * updateKeyPose (src/mapOptmization.cpp:310) and getLoopLocalMap (:214) use it, for n_clouds
+ * ragged clouds, each by its own pose, in one launch (the map cloud of correctPoses, :315-332).
+ *   d_xyzi / d_out  float4 points; cloud c is points [off[c], off[c + 1]) of both (output at the
+ *                   SAME offsets).  d_out must not alias d_xyzi.
+ *   d_off / h_off   int64, n_clouds + 1, device and host copies.  off[0] may be non-zero (pass
+ *                   d_off + first and h_off + first to transform clouds first ... first + n - 1);
+ *                   points outside [off[0], off[n_clouds]) are not touched.
+ *   d_T             12 doubles per cloud: the top three rows of the 4x4, row-major
+ *                   (R[r][0], R[r][1], R[r][2], t[r]).
+ * Per output row, as PCL 1.10's detail::Transformer<double>::se3 writes it:
+ *   (float)(((T[r][0]*(double)x + T[r][1]*(double)y) + T[r][2]*(double)z) + T[r][3])
+ * left to right in double, one rounding to float, no fused multiply-add; intensity is copied bit
+ * for bit.  n_clouds == 0 and an all-empty range return SSF_OK without a launch.  Asynchronous
+ * on stream.
+ */
+int32_t ssf_transform_clouds_batch(ssf_ctx* ctx, void* stream, int32_t n_clouds, const float* d_xyzi,
+                                   const int64_t* d_off, const int64_t* h_off, const double* d_T,
+                                   float* d_out);
+
 /* ssf_icp_batch replaces pcl::IterativeClosestPoint<PointXYZI, PointXYZI>::align +
  * hasConverged + getFitnessScore + getFinalTransformation as addLoopFactor() uses them
  * (src/mapOptmization.cpp:224-238): n_prob independent (source, target) problems, float4

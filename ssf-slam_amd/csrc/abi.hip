@@ -921,6 +921,28 @@ int32_t ssf_voxel_grid_batch(ssf_ctx* c, void* stream, int32_t n_clouds, const f
     return SSF_OK;
 }
 
+int32_t ssf_transform_clouds_batch(ssf_ctx* c, void* stream, int32_t n_clouds, const float* d_xyzi,
+                                   const int64_t* d_off, const int64_t* h_off, const double* d_T,
+                                   float* d_out) {
+    if (!c) return SSF_E_ARG;
+    if (n_clouds < 0 || (n_clouds > 0 && (!d_xyzi || !d_off || !h_off || !d_T || !d_out)))
+        return fail(c, SSF_E_ARG, "transform_clouds_batch: bad arguments");
+    if (n_clouds == 0) return SSF_OK;
+    if (d_out == d_xyzi) return fail(c, SSF_E_ARG, "transform_clouds_batch: the output aliases the input");
+    for (int k = 0; k < n_clouds; ++k)
+        if (h_off[k + 1] < h_off[k]) return fail(c, SSF_E_ARG, "transform_clouds_batch: offsets not monotone");
+    if (h_off[0] < 0) return fail(c, SSF_E_ARG, "transform_clouds_batch: negative offset");
+    const int64_t total = h_off[n_clouds] - h_off[0];
+    if (total == 0) return SSF_OK;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(c, stream);
+    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    hipError_t e = ssf::launch_transform_clouds(s, n_clouds, reinterpret_cast<const float4*>(d_xyzi), d_off,
+                                                h_off[0], total, d_T, reinterpret_cast<float4*>(d_out));
+    if (e != hipSuccess) return hip_fail(c, e, "transform_clouds launch");
+    return SSF_OK;
+}
+
 int32_t ssf_icp_params_default(ssf_icp_params* out) {
     if (!out) return SSF_E_ARG;
     out->max_iter = 100;            // mapOptmization.cpp:225-228

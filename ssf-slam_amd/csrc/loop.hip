@@ -6,7 +6,10 @@
 //                64-bit (cloud, voxel) keys, a stable hipCUB radix sort of (key, point), run
 //                heads + scan, and one thread per voxel summing its run in input order (float,
 //                as PCL's Eigen::VectorXf centroid) -- bit-exact with the oracle.
-//   ICP          pcl::IterativeClosestPoint<PointXYZI, PointXYZI> (:224-236): per iteration
+//   transform    pcl::transformPointCloud(cloud, out, Eigen::Affine3d) (updateKeyPose :310,
+//                getLoopLocalMap :214) for many ragged clouds, each by its own pose, in one
+//                streaming launch (the map cloud of correctPoses :315-332).
+//   ICP         pcl::IterativeClosestPoint<PointXYZI, PointXYZI> (:224-236): per iteration
 //                (a) exact 1-NN of every transformed source point against its target cloud,
 //                brute force over target tiles staged in LDS, the (distance, index) pairs packed
 //                into u64 keys merged with atomicMin (lexicographic = FLANN L2_Simple distance,
@@ -185,6 +188,76 @@ hipError_t launch_voxel_grid(hipStream_t s, int n_clouds, const float4* pts, con
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_vg_reduce, dim3(g), dim3(256), 0, s, pts, off, n_clouds, k1, v1, head, vid, n,
                        out, out_count);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// rigid transform of many ragged clouds (pcl::transformPointCloud with an Affine3d, as
+// updateKeyPose :310 and getLoopLocalMap :214 call it).  Memory-bound, 16 B in and 16 B out per
+// point: one flat index over the points of all clouds, tiles of kTfTile points per work-group
+// (a wave touches 1 KiB contiguous per access, kTfPerThread accesses per thread), a capped grid
+// with a grid-stride loop over the tiles.  A work-group finds the cloud of its tile's first point
+// with one binary search over the offsets; its threads walk forward from there (runs of empty
+// clouds included) and reload the 12 doubles of a pose only when the cloud changes.
+constexpr int kTfThreads = 256;
+constexpr int kTfPerThread = 4;
+constexpr int kTfTile = kTfThreads * kTfPerThread;
+constexpr int kTfMaxBlocks = 2048;       // 256 CUs x 8 work-groups
+
+// PCL 1.10 detail::Transformer<double>::se3, one row: left to right in double, one rounding
+SSF_DEV float tf_row(const double* T, double x, double y, double z) {
+    return (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
+}
+
+// off: n_clouds + 1 offsets; base = off[0] and total = off[n_clouds] - off[0] as the host read
+// them (the points written are exactly [base, base + total)); T: 12 doubles per cloud.
+__global__ __launch_bounds__(kTfThreads) void k_transform_clouds(const float4* __restrict__ in,
+                                                                 const int64_t* __restrict__ off,
+                                                                 int n_clouds, int64_t base, int64_t total,
+                                                                 const double* __restrict__ T,
+                                                                 float4* __restrict__ out) {
+    const int64_t end = base + total;
+    const int64_t n_tiles = (total + kTfTile - 1) / kTfTile;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t i0 = base + tile * kTfTile;
+        // the last cloud whose offset is <= i0: it holds point i0 (off[lo] <= i0 < off[hi])
+        int lo = 0, hi = n_clouds;
+        while (hi - lo > 1) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (off[mid] <= i0) lo = mid; else hi = mid;
+        }
+        float4 p[kTfPerThread];
+#pragma unroll
+        for (int k = 0; k < kTfPerThread; ++k) {
+            const int64_t i = i0 + k * kTfThreads + threadIdx.x;
+            if (i < end) p[k] = in[i];
+        }
+        int c = lo, loaded = -1;
+        double M[12];
+#pragma unroll
+        for (int k = 0; k < kTfPerThread; ++k) {
+            const int64_t i = i0 + k * kTfThreads + threadIdx.x;
+            if (i >= end) break;
+            while (c + 1 < n_clouds && i >= off[c + 1]) ++c;
+            if (c != loaded) {
+#pragma unroll
+                for (int j = 0; j < 12; ++j) M[j] = T[(int64_t)c * 12 + j];
+                loaded = c;
+            }
+            const double x = (double)p[k].x, y = (double)p[k].y, z = (double)p[k].z;
+            out[i] = make_float4(tf_row(M, x, y, z), tf_row(M + 4, x, y, z), tf_row(M + 8, x, y, z), p[k].w);
+        }
+    }
+}
+
+hipError_t launch_transform_clouds(hipStream_t s, int n_clouds, const float4* in, const int64_t* off,
+                                   int64_t base, int64_t total, const double* T, float4* out) {
+    if (n_clouds <= 0 || total <= 0) return hipSuccess;
+    const int64_t n_tiles = (total + kTfTile - 1) / kTfTile;
+    const int grid = (int)(n_tiles < (int64_t)kTfMaxBlocks ? n_tiles : (int64_t)kTfMaxBlocks);
+    kmark(s, "k_transform_clouds");
+    hipLaunchKernelGGL(k_transform_clouds, dim3(grid), dim3(kTfThreads), 0, s, in, off, n_clouds, base, total,
+                       T, out);
     return hipGetLastError();
 }
 

@@ -191,6 +191,10 @@ size_t vg_scratch_bytes(int n_clouds, int64_t n);
 hipError_t launch_voxel_grid(hipStream_t s, int n_clouds, const float4* pts, const int64_t* off,
                              int64_t n, int64_t max_pts, float leaf, void* scratch, float4* out,
                              int32_t* out_count);
+// clouds [off[c], off[c + 1]) of in -> out at the same offsets, cloud c by the 12 doubles at
+// T + 12 c; base = off[0], total = off[n_clouds] - off[0] (host values)
+hipError_t launch_transform_clouds(hipStream_t s, int n_clouds, const float4* in, const int64_t* off,
+                                   int64_t base, int64_t total, const double* T, float4* out);
 hipError_t launch_icp_init(hipStream_t s, int n_prob, const float4* src, const int64_t* soff,
                            int64_t max_ns, const float* guess, float4* cur, IcpState* st,
                            unsigned long long* key);

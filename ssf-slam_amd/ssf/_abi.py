@@ -40,6 +40,7 @@ EXPORTS = [
     "ssf_edge_config_default", "ssf_set_edge_config", "ssf_extract_features_batch",
     "ssf_edge_table_batch", "ssf_register_batch_edges", "ssf_kabsch_f32_batch",
     "ssf_set_mask_schedule", "ssf_register_plan", "ssf_pgo_params_default", "ssf_pose_graph_batch",
+    "ssf_transform_clouds_batch",
 ]
 # Every symbol include/ssf_pointnet2.h declares (TFlow point-set operators).
 PN2_EXPORTS = [
@@ -182,6 +183,8 @@ def lib():
     L.ssf_accumulate_sequence.restype = i32
     L.ssf_voxel_grid_batch.argtypes = [vp, vp, i32, vp, vp, vp, C.c_float, vp, vp]
     L.ssf_voxel_grid_batch.restype = i32
+    L.ssf_transform_clouds_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.ssf_transform_clouds_batch.restype = i32
     L.ssf_icp_params_default.argtypes = [C.POINTER(IcpParams)]
     L.ssf_icp_params_default.restype = i32
     L.ssf_icp_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(IcpParams), vp, vp]

@@ -125,8 +125,13 @@ def node_main(exe: str, argv=None):
                          queue_size=10)
     else:
         path = rospy.get_param("~RESULT_PATH") if rospy.has_param("~RESULT_PATH") else None
-        pub = rosbridge.RosPublisher(["/map_odom_res3", "/map_frame_res3", "/map_laser_path_res3"])
-        node = nodes.MapOptimizationNode(pub, device=a.device, tum_path=path)
+        # ~MAP_CLOUD (not a reference param, default false): keep the map cloud on the GPU and
+        # publish /sum_map_cloud_res3 (mapOptmization.cpp:387-397, 476)
+        map_cloud = bool(rospy.get_param("~MAP_CLOUD")) if rospy.has_param("~MAP_CLOUD") else False
+        topics = ["/map_odom_res3", "/map_frame_res3", "/map_laser_path_res3"]
+        pub = rosbridge.RosPublisher(topics + (["/sum_map_cloud_res3"] if map_cloud else []))
+        node = nodes.MapOptimizationNode(pub, device=a.device, tum_path=path,
+                                         **(dict(map_cloud=True) if map_cloud else {}))
         rospy.Subscriber("/plane_frame_cloud2", sensor_msgs.PointCloud2, node.on_plane_cloud,
                          queue_size=10)                               # mapOptmization.cpp:473
         rospy.Subscriber("/frame_odom2", nav_msgs.Odometry,

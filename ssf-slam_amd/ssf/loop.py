@@ -11,7 +11,10 @@ noise = the ICP fitness score).  By default the published pose is the loop-adjus
 ``LoopCloser(optimize=True)`` also records the factors of addOdomFactor (:147-165), optimises
 the pose graph on the GPU at every loop closure (``optimize_pose_graphs`` <- runOptimize
 :280-293, batched Gauss-Newton in pose_graph.hip, not GTSAM's iSAM2) and rewrites every
-keyframe pose (correctPoses :296-332), see DESIGN.md §6.7.
+keyframe pose (correctPoses :296-332), see DESIGN.md §6.7.  ``LoopCloser(map_cloud=True)`` also
+keeps the accumulated map cloud (mapCloudPtr: updateKeyPose :309-311, the rebuild of
+correctPoses :320-325) on the device in an ``ssf.MapCloud``; a new keyframe
+goes into the map at its stored key pose (the reference places it at its iSAM2 estimate).
 
 Pose helpers restate pcl/common/eigen.h: getTransformation (roll/pitch/yaw -> affine,
 yaw * pitch * roll) and getTranslationAndEulerAngles.  Key poses are stored in float, as the
@@ -245,6 +248,28 @@ class LoopCloser:
     graph_edges: list = field(default_factory=list)    # (i, j, measurement 7 doubles, 6 variances)
     graph_prior: np.ndarray | None = None
     last_optimization: dict | None = None
+    # map_cloud=True: the keyframe clouds live in a device store and the accumulated map
+    # (mapCloudPtr, updateKeyPose :309-311) is kept equal to every keyframe under its current key
+    # pose: appended per keyframe, rebuilt in one launch when the poses are rewritten
+    map_cloud: bool = False
+    map: object | None = None                          # ssf.MapCloud when map_cloud, else None
+
+    def __post_init__(self):
+        if self.map_cloud and self.map is None:
+            from .map_cloud import MapCloud
+            self.map = MapCloud(self.fe)
+
+    def _store_key_frame(self, plane_xyzi):
+        """keyFrameVector.push_back (:406) into the map's store: key_frames[k] is its view there."""
+        gen = self.map.generation
+        self.key_frames.append(self.map.store(plane_xyzi))
+        if self.map.generation != gen:                 # the store moved: drop the views of the old one
+            self.key_frames[:] = [self.map.keyframe(k) for k in range(self.map.n_keyframes)]
+
+    def rebuild_map(self):
+        """mapCloudPtr->clear() and updateKeyPose for every keyframe (:320-325), one launch."""
+        K = self.map.n_keyframes
+        self.map.transform(0, K, [self._T6(i) for i in range(K)])
 
     def _T6(self, i):
         p = self.key6d[i]
@@ -342,6 +367,8 @@ class LoopCloser:
             six = get_translation_and_euler_angles(pose_from_quat(p[:4], p[4:]))
             self.key6d[i][:6] = np.array(six, np.float32).tolist()
             self.graph_init[i] = np.array(p, np.float64)
+        if self.map is not None:                            # the aLoopIsClosed branch (:318-326)
+            self.rebuild_map()
         return self._T6(-1)
 
     def process(self, plane_xyzi: torch.Tensor, q_xyzw, t, stamp: float):
@@ -352,14 +379,22 @@ class LoopCloser:
             return T, None, False
         x, y, z, r, p, yw = get_translation_and_euler_angles(T)
         self.key6d.append(np.array([x, y, z, r, p, yw], np.float32).tolist() + [float(stamp)])
-        self.key_frames.append(plane_xyzi.contiguous())
+        if self.map is not None:
+            self._store_key_frame(plane_xyzi)
+        else:
+            self.key_frames.append(plane_xyzi.contiguous())
         if self.optimize:
             self._add_odom_factor((x, y, z, r, p, yw))
         c = self.add_loop_factor()
+        rebuilt = False
         if c is not None:                                   # correctPoses (:321-326)
             if self.optimize:
-                T = self.close_loop(c)
+                T = self.close_loop(c)                      # rebuilds the map, this keyframe included
+                rebuilt = True
             self.trans_loop_adjust = self.trans_loop_adjust @ c.correction
+        if self.map is not None and not rebuilt:            # updateKeyPose(numPoses - 1) (:329)
+            k = len(self.key6d) - 1
+            self.map.transform(k, k + 1, [self._T6(k)])
         return T, c, True
 
     def add_loop_edge(self, c: LoopConstraint):

@@ -256,14 +256,23 @@ class MapOptimizationNode:
     optimize=True: a loop closure also optimises the pose graph on the GPU and rewrites every
     keyframe pose (runOptimize / correctPoses, :280-332; ``closer.key6d``,
     ``closer.last_optimization``); the keyframe that closed the loop is published at its
-    corrected pose."""
+    corrected pose.
+    map_cloud=True: the accumulated map (mapCloudPtr) is kept on the device (``closer.map``)
+    and its 0.4 m VoxelGrid is published on /sum_map_cloud_res3 for every keyframe whose pair
+    count numFrame (first pair = 1) is a multiple of 5 (publishResult :387-397)."""
 
     def __init__(self, publish, device=None, frontend: Frontend | None = None,
-                 tum_path: str | None = None, optimize: bool = False):
+                 tum_path: str | None = None, optimize: bool = False, map_cloud: bool = False):
         from .loop import LoopCloser, get_translation_and_euler_angles  # noqa: F401
         self.publish = publish
         self.fe = frontend or Frontend(64, device=device)
-        self.closer = LoopCloser(self.fe, optimize=True) if optimize else LoopCloser(self.fe)
+        kw = dict(optimize=True) if optimize else {}
+        if map_cloud:
+            kw["map_cloud"] = True
+        self.closer = LoopCloser(self.fe, **kw)
+        self.map_cloud = bool(map_cloud)
+        self.num_frame = 0                        # numFrame (:433): synchronised pairs
+        self.map_published = 0
         self.planes, self.odoms = [], []          # planeQueue / odometryQueue (:65-75)
         self.path = Path()
         self.writer = sio.TumWriter(tum_path) if tum_path else None
@@ -289,7 +298,8 @@ class MapOptimizationNode:
             self.odoms.pop(0)
             xyzi = torch.from_numpy(sio.cloud_xyzi(pm)).to(self.fe.device)
             stamp = tp[0] + tp[1] * 1e-9
-            T, _, _ = self.closer.process(xyzi, om.pose.orientation, om.pose.position, stamp)
+            self.num_frame += 1
+            T, _, is_key = self.closer.process(xyzi, om.pose.orientation, om.pose.position, stamp)
             q = Rotation.from_matrix(T[:3, :3]).as_quat()                  # x, y, z, w
             hdr = sio.Header(tp[0], tp[1], "map")
             pose = Pose(tuple(float(v) for v in T[:3, 3]), tuple(float(v) for v in q))
@@ -300,6 +310,9 @@ class MapOptimizationNode:
             self.path.header = hdr
             self.publish("/map_laser_path_res3", self.path)
             self.publish("/map_frame_res3", sio.xyzi_to_cloud(transform_cloud(xyzi, T), tp, "map"))
+            if self.map_cloud and is_key and self.num_frame % 5 == 0:      # :388-397
+                self.publish("/sum_map_cloud_res3", sio.xyzi_to_cloud(self.closer.map.filtered(0.4), tp, "map"))
+                self.map_published += 1
 
 
 LAUNCH_GRAPHS = {
@@ -313,7 +326,7 @@ LAUNCH_GRAPHS = {
 def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, device=None,
                  solver: str = "ceres_lm", max_iter: int | None = None, seed: int | None = None,
                  rate_hz: float = 10.0, launch: str = "onlyPC", map_tum_path: str | None = None,
-                 truncate_results: bool = False, map_optimize: bool = False):
+                 truncate_results: bool = False, map_optimize: bool = False, map_cloud: bool = False):
     """Replay a DATASET_PATH directory through the node graph of launch/run_<launch>.launch:
       onlyPC: PointCloudOdometry_onlyPC -> frameFeature -> lidarOdometry_onlyPC (registration)
       noSeg:  PointCloudOdometry_noSeg (GMM mask + Kabsch -> /frame_odom1) -> frameFeature ->
@@ -325,9 +338,13 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
     appended to `tum_path` as TUM lines (like the reference, an existing file is extended unless
     truncate_results=True).
     -> dict(odom1 [F, 7] f64 [t, q] (empty for onlyPC), odom2 [F-1, 7] f64 [t, q], stamps, loops;
-    with map_optimize also optimization (the last solve) and key_poses)"""
+    with map_optimize also optimization (the last solve) and key_poses; with map_cloud (needs
+    map_tum_path) also map_cloud, the final 0.4 m map as float32 [M, 4], map_cloud_published,
+    the number of /sum_map_cloud_res3 messages, and map_cloud_keyframes)"""
     if launch not in LAUNCH_GRAPHS:
         raise ValueError(f"launch {launch!r}: one of {sorted(LAUNCH_GRAPHS)}")
+    if map_cloud and map_tum_path is None:
+        raise ValueError("map_cloud needs mapOptmization in the graph: pass map_tum_path")
     src_mode, odo_kind, keys = LAUNCH_GRAPHS[launch]
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     bus = Bus()
@@ -360,8 +377,10 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
     if map_tum_path is not None:                     # mapOptmization on /plane_frame_cloud2 + /frame_odom2
         if map_tum_path and truncate_results:
             open(map_tum_path, "w").close()
-        mo = (MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None, optimize=True)
-              if map_optimize else MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None))
+        mkw = dict(optimize=True) if map_optimize else {}
+        if map_cloud:
+            mkw["map_cloud"] = True
+        mo = MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None, **mkw)
         bus.subscribe("/plane_frame_cloud2", mo.on_plane_cloud)
         bus.subscribe("/frame_odom2", mo.on_odom)
     period_ns = int(round(1e9 / rate_hz))
@@ -377,4 +396,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
     if map_optimize:                                 # the last solve (None: no loop was closed)
         res["optimization"] = mo.closer.last_optimization if mo else None
         res["key_poses"] = [list(k) for k in mo.closer.key6d] if mo else []
+    if map_cloud:                                    # the map as it stands, filtered once
+        res["map_cloud"] = mo.closer.map.filtered(0.4).cpu().numpy()
+        res["map_cloud_published"] = mo.map_published
+        res["map_cloud_keyframes"] = mo.closer.map.n_keyframes
     return res

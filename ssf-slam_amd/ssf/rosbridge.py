@@ -118,6 +118,7 @@ TOPICS = {
     "/map_odom_res3": ("nav_msgs", "Odometry", "odom", 100),              # mapOptmization.cpp:471-478
     "/map_frame_res3": ("sensor_msgs", "PointCloud2", "cloud", 10),       # mapOptmization.cpp:475
     "/map_laser_path_res3": ("nav_msgs", "Path", "path", 100),
+    "/sum_map_cloud_res3": ("sensor_msgs", "PointCloud2", "cloud", 10),   # mapOptmization.cpp:476
 }
 
 

@@ -1,7 +1,8 @@
 """python -m ssf.run DATASET_PATH [--launch noSeg] [--tum traj.txt]: replay an npz scene-flow
 sequence through the device front-end as one of the reference's launch files wires its nodes
 (launch/run_onlyPC.launch, run_noSeg.launch, run_Seg.launch; ssf.nodes.LAUNCH_GRAPHS) and append
-/frame_odom2 to a TUM trajectory (optionally with mapOptmization's loop closure)."""
+/frame_odom2 to a TUM trajectory (optionally with mapOptmization's loop closure, and with
+--map-cloud its accumulated map cloud saved as an npy file)."""
 from __future__ import annotations
 
 import argparse
@@ -28,6 +29,9 @@ def main(argv=None):
     ap.add_argument("--map-optimize", action="store_true",
                     help="with --map-tum: optimise the pose graph on a loop closure and rewrite the "
                          "keyframe poses (runOptimize / correctPoses)")
+    ap.add_argument("--map-cloud", default=None, metavar="FILE.npy",
+                    help="with --map-tum: keep the accumulated map cloud on the GPU, publish its 0.4 m "
+                         "VoxelGrid on /sum_map_cloud_res3 and save the final one as float32 [M, 4]")
     ap.add_argument("--rate-hz", type=float, default=10.0,
                     help="frame rate of the synthetic stamps (frame k at k / rate)")
     a = ap.parse_args(argv)
@@ -37,15 +41,24 @@ def main(argv=None):
     if a.tum and os.path.exists(a.tum) and not a.truncate:
         print(f"ssf.run: appending to the existing {a.tum} (the reference's std::ios::app); "
               f"--truncate starts a new file", file=sys.stderr)
+    if a.map_cloud and a.map_tum is None:
+        ap.error("--map-cloud needs --map-tum")
     torch.cuda.set_device(a.device)
+    kw = dict(map_cloud=True) if a.map_cloud else {}
     res = run_sequence(a.dataset_path, a.tum, n_rows=a.rows, solver=a.solver, max_iter=a.iters,
                        seed=a.seed, launch=a.launch, map_tum_path=a.map_tum, map_optimize=a.map_optimize,
-                       truncate_results=a.truncate, rate_hz=a.rate_hz)
+                       truncate_results=a.truncate, rate_hz=a.rate_hz, **kw)
     extra = {}
     if a.map_optimize:
         opt = res["optimization"]
         extra = {"map_optimize": None if opt is None else
                  {k: opt[k] for k in ("status_name", "iterations", "cost0", "cost", "loops")}}
+    if a.map_cloud:
+        import numpy as np
+        with open(a.map_cloud, "wb") as f:           # the name as given (np.save appends .npy to a path)
+            np.save(f, res["map_cloud"])
+        extra["map_cloud"] = {"file": a.map_cloud, "points": int(res["map_cloud"].shape[0]),
+                              "keyframes": int(res["map_cloud_keyframes"])}
     print(json.dumps({"launch": a.launch, "tum": a.tum, "tum_mode": "truncate" if a.truncate else "append",
                       "frames": len(res["stamps"]),
                       "odom1_poses": int(res["odom1"].shape[0]),
