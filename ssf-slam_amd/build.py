@@ -13,11 +13,12 @@ OUT_DIR = os.path.join(HERE, "ssf", "_lib")
 OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libssf_frontend.so")
 SYNTH_LIB = os.path.join(OUT_DIR, "libssf_synth.so")
-SOURCES = ["abi.hip", "features.hip", "registration.hip", "mask_pose.hip", "mask_pose_f64.hip", "kabsch_f32.hip",
-           "loop.hip", "pose_graph.hip", "pointnet2.hip"]
+SOURCES = ["abi.hip", "features.hip", "plane_table.hip", "associate.hip", "edges.hip", "solve.hip", "mask_pose.hip",
+           "mask_pose_f64.hip", "kabsch_f32.hip", "loop.hip", "pose_graph.hip", "pointnet2.hip"]
 # sources that include another source file
 SRC_DEPS = {"mask_pose_f64.hip": ["mask_pose.hip"]}
-HEADERS = ["ssf_device.hpp", "ssf_internal.hpp", "svd3.hpp", os.path.join("..", "..", "include", "ssf_frontend.h"),
+HEADERS = ["ssf_device.hpp", "ssf_internal.hpp", "reg_knn.hpp", "reg_strips.hpp", "svd3.hpp",
+           os.path.join("..", "..", "include", "ssf_frontend.h"),
            os.path.join("..", "..", "include", "ssf_pointnet2.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: no FMA contraction, so float stages match the reference's x86 arithmetic
@@ -37,35 +38,45 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
+def _run(cmd, verbose=False):
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+    return r
+
+
+def _compile_link(out: str, suffix: str = "", extra: dict = None, force: bool = True,
+                  verbose: bool = False) -> str:
+    """Compile SOURCES (FLAGS, the file's FILE_FLAGS, then extra[file]) into build/<file><suffix>.o,
+    4 at a time, and link the objects into `out`.  force=False: only what is older than its
+    source, a header or a source it includes."""
     os.makedirs(OUT_DIR, exist_ok=True)
     os.makedirs(OBJ_DIR, exist_ok=True)
+    extra = extra or {}
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
-        o = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
+        o = os.path.join(OBJ_DIR, src.replace(".hip", suffix + ".o"))
         objs.append(o)
         if force or _stale(o, [s] + hdrs + [os.path.join(CSRC, d) for d in SRC_DEPS.get(src, [])]):
-            jobs.append([HIPCC, *FLAGS, *FILE_FLAGS.get(src, []), "-c", s, "-o", o])
-
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
-        return r
-
+            jobs.append([HIPCC, *FLAGS, *FILE_FLAGS.get(src, []), *extra.get(src, []), "-c", s, "-o", o])
     with ThreadPoolExecutor(max_workers=min(4, max(1, len(jobs)))) as ex:
-        list(ex.map(run, jobs))
-    if force or jobs or _stale(LIB, objs):
-        run([HIPCC, *FLAGS, "-shared", *objs, "-o", LIB])
+        list(ex.map(lambda cmd: _run(cmd, verbose), jobs))
+    if force or jobs or _stale(out, objs):
+        _run([HIPCC, *FLAGS, "-shared", *objs, "-o", out], verbose)
+    return out
+
+
+def build(force: bool = False, verbose: bool = False) -> str:
+    _compile_link(LIB, force=force, verbose=verbose)
     # bench / test data generator (ssf.synth.BatchScanner): a library of its own, not the front-end
     syn = os.path.join(CSRC, "synth.hip")
     if force or _stale(SYNTH_LIB, [syn]):
-        run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-shared", syn,
-             "-o", SYNTH_LIB])
+        _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-shared", syn,
+              "-o", SYNTH_LIB], verbose)
     return LIB
 
 
@@ -95,32 +106,17 @@ def build_diag() -> str:
     """Diagnostic library (phase stamps in k_mask_pose, -DSSF_MASK_STAMPS, and in
     k_plane_table_sorted, -DSSF_TABLE_STAMPS) for tools/diag_mask_phases.py and
     tools/diag_table_phases.py; never loaded by the product path unless SSF_LIB points at it."""
-    out = os.path.join(OUT_DIR, "libssf_frontend_diag.so")
-    objs = []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(OBJ_DIR, src.replace(".hip", "_diag.o"))
-        extra = {"mask_pose.hip": ["-DSSF_MASK_STAMPS"], "mask_pose_f64.hip": ["-DSSF_MASK_STAMPS"],
-                 "registration.hip": ["-DSSF_TABLE_STAMPS"]}.get(src, [])
-        subprocess.run([HIPCC, *FLAGS, *FILE_FLAGS.get(src, []), *extra, "-c", s, "-o", o], check=True)
-        objs.append(o)
-    subprocess.run([HIPCC, *FLAGS, "-shared", *objs, "-o", out], check=True)
-    return out
+    stamps = {"mask_pose.hip": ["-DSSF_MASK_STAMPS"], "mask_pose_f64.hip": ["-DSSF_MASK_STAMPS"],
+              "plane_table.hip": ["-DSSF_TABLE_STAMPS"]}
+    return _compile_link(os.path.join(OUT_DIR, "libssf_frontend_diag.so"), "_diag", stamps)
 
 
 def build_variant(name: str, defines: dict) -> str:
     """Experiment library (tools/ only, loaded through SSF_LIB): every source compiled with extra
     -D defines into ssf/_lib/libssf_frontend_<name>.so.  Never loaded by the product path."""
-    out = os.path.join(OUT_DIR, f"libssf_frontend_{name}.so")
     extra = [f"-D{k}={v}" for k, v in defines.items()]
-    objs = []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(OBJ_DIR, src.replace(".hip", f"_{name}.o"))
-        subprocess.run([HIPCC, *FLAGS, *FILE_FLAGS.get(src, []), *extra, "-c", s, "-o", o], check=True)
-        objs.append(o)
-    subprocess.run([HIPCC, *FLAGS, "-shared", *objs, "-o", out], check=True)
-    return out
+    return _compile_link(os.path.join(OUT_DIR, f"libssf_frontend_{name}.so"), f"_{name}",
+                         {src: extra for src in SOURCES})
 
 
 if __name__ == "__main__":

@@ -409,13 +409,20 @@ static int32_t extract_planes_impl(ssf_ctx* c, void* stream, int32_t n_frames, c
         SSF_TRY_HIP(c, c->fcurv.ensure(sizeof(float) * (size_t)std::max<int64_t>(total_points, 1)), "alloc chunk curvature");
     ssf::FeatScratch fs{c->rtab.p, c->fcnt.as<int32_t>(), c->fidx.as<uint16_t>(), c->fbits.as<uint64_t>(),
                         c->fcurv.as<float>(), c->firr.as<uint8_t>(), c->flmap.as<uint8_t>()};
+    ssf::BinScratch bin{};
+    bin.rid = c->rid.as<int8_t>(); bin.hist = c->hist.as<int32_t>();
+    bin.ring_idx = c->ring_xyzi.as<int32_t>(); bin.flags = c->sel_cnt.as<uint8_t>(); bin.fix = c->fix.p;
+    ssf::FeatFrames in{};
+    in.pts = d_pts; in.stride = point_stride; in.frame_off = d_frame_off;
+    in.max_pts = max_frame_points; in.keep = d_keep;
+    ssf::FeatOut out{};
+    out.plane = reinterpret_cast<float4*>(d_plane_xyzi); out.plane_count = d_plane_count;
+    out.ring_off = d_ring_off ? d_ring_off : c->ring_off.as<int32_t>();
+    out.ring_xyzi = ring4; out.curv = d_curv;
+    const ssf::EdgeSel* edge = edges ? &es : nullptr;
     ProfScope prof(c, stream);
-    int32_t* roff = d_ring_off ? d_ring_off : c->ring_off.as<int32_t>();
-    hipError_t e = ssf::launch_extract_planes(
-        (hipStream_t)stream, c->cfg, n_frames, d_pts, point_stride, d_frame_off, max_frame_points,
-        d_keep, c->rid.as<int8_t>(), c->hist.as<int32_t>(), roff, c->ring_xyzi.as<int32_t>(), ring4,
-        d_curv, c->sel_cnt.as<uint8_t>(), c->fix.p, c->sel.as<int32_t>(),
-        reinterpret_cast<float4*>(d_plane_xyzi), d_plane_count, edges ? &es : nullptr, &fs);
+    hipError_t e = ssf::launch_extract_planes((hipStream_t)stream, c->cfg, n_frames, in, out,
+                                              c->sel.as<int32_t>(), bin, fs, edge);
     if (e != hipSuccess) return hip_fail(c, e, "extract_planes launch");
     return SSF_OK;
 }
@@ -548,13 +555,18 @@ int32_t ssf_register_batch(ssf_ctx* c, void* stream, int32_t n_pairs, const floa
     const size_t nq = (size_t)std::max<int64_t>(curr_total_points, 1);
     SSF_TRY_HIP(c, c->cidx.ensure(sizeof(int32_t) * (nq + (size_t)n_pairs)), "alloc corr index");
     ProfScope prof(c, stream);
-    hipError_t e = ssf::launch_register(
-        (hipStream_t)stream, c->cfg, n_pairs, reinterpret_cast<const float4*>(d_last_xyzi), d_last_off,
-        d_last_count, d_last_normal, d_last_valid, reinterpret_cast<const float4*>(d_last_sorted_xyzi),
-        d_last_sorted_idx, reinterpret_cast<const float4*>(d_curr_xyzi), d_curr_off,
-        d_curr_count, max_plane_points, c->corr.as<ssf::CorrRec>(), d_pose_rel, d_pose_abs, d_log,
-        d_nlog, d_ncorr, d_nn, nullptr, reinterpret_cast<const float4*>(d_last_strip_xyzi),
-        d_last_strip_head, nullptr, nullptr, c->cidx.as<int32_t>(), c->cidx.as<int32_t>() + nq);
+    ssf::RegisterArgs a{};
+    a.last.xyzi = reinterpret_cast<const float4*>(d_last_xyzi); a.last.off = d_last_off; a.last.count = d_last_count;
+    a.table.normal = d_last_normal; a.table.valid = d_last_valid;
+    a.table.sorted = reinterpret_cast<const float4*>(d_last_sorted_xyzi); a.table.sidx = d_last_sorted_idx;
+    a.table.strip_xyzi = reinterpret_cast<const float4*>(d_last_strip_xyzi); a.table.strip_head = d_last_strip_head;
+    a.curr.xyzi = reinterpret_cast<const float4*>(d_curr_xyzi); a.curr.off = d_curr_off; a.curr.count = d_curr_count;
+    a.pose.rel = d_pose_rel; a.pose.abs = d_pose_abs;
+    a.out.log = d_log; a.out.nlog = d_nlog; a.out.ncorr = d_ncorr; a.out.nn = d_nn;
+    a.scratch.corr = c->corr.as<ssf::CorrRec>();
+    a.scratch.nnv = c->cidx.as<int32_t>(); a.scratch.ncompact = c->cidx.as<int32_t>() + nq;
+    a.max_m = max_plane_points;
+    hipError_t e = ssf::launch_register((hipStream_t)stream, c->cfg, n_pairs, a);
     if (e != hipSuccess) return hip_fail(c, e, "register launch");
     return SSF_OK;
 }
@@ -595,17 +607,24 @@ int32_t ssf_register_chain(ssf_ctx* c, void* stream, int32_t n_pairs, const floa
     // pair k = (frame k, frame k + 1) of the same arrays: its warm start is pair k - 1's output
     // slot (lidarOdometry_onlyPC.cpp:164,251-252), read in place by the association and the
     // solve -- no copy between the links, two launches per pair, all enqueued here
-    const float4* X = reinterpret_cast<const float4*>(d_xyzi);
+    ssf::RegisterArgs a{};                         // no log, no 1-NN output, no compaction scratch
+    a.last.xyzi = a.curr.xyzi = reinterpret_cast<const float4*>(d_xyzi);
+    a.table.normal = d_normal; a.table.valid = d_valid;
+    a.table.sorted = reinterpret_cast<const float4*>(d_sorted_xyzi); a.table.sidx = d_sorted_idx;
+    a.table.strip_xyzi = reinterpret_cast<const float4*>(d_strip_xyzi); a.table.strip_head = d_strip_head;
+    a.scratch.corr = c->corr.as<ssf::CorrRec>();
+    a.max_m = max_plane_points;
     for (int k = 0; k < n_pairs; ++k) {
-        hipError_t e = ssf::launch_register(
-            (hipStream_t)stream, c->cfg, 1, X, d_off + k, d_count + k, d_normal, d_valid,
-            reinterpret_cast<const float4*>(d_sorted_xyzi), d_sorted_idx, X, d_off + k + 1,
-            d_count + k + 1, max_plane_points, c->corr.as<ssf::CorrRec>(), d_pose_seq + 7 * k,
-            d_pose_abs_seq ? d_pose_abs_seq + 7 * k : nullptr, nullptr, nullptr,
-            d_ncorr ? d_ncorr + k : nullptr, nullptr, nullptr,
-            reinterpret_cast<const float4*>(d_strip_xyzi), d_strip_head,
-            k == 0 ? d_pose_init : d_pose_seq + 7 * (k - 1),
-            d_pose_abs_seq ? (k == 0 ? d_pose_abs_init : d_pose_abs_seq + 7 * (k - 1)) : nullptr);
+        a.last.off = d_off + k; a.last.count = d_count + k;
+        a.curr.off = d_off + k + 1; a.curr.count = d_count + k + 1;
+        a.pose.in = k == 0 ? d_pose_init : d_pose_seq + 7 * (k - 1);
+        a.pose.rel = d_pose_seq + 7 * k;
+        if (d_pose_abs_seq) {
+            a.pose.abs_in = k == 0 ? d_pose_abs_init : d_pose_abs_seq + 7 * (k - 1);
+            a.pose.abs = d_pose_abs_seq + 7 * k;
+        }
+        if (d_ncorr) a.out.ncorr = d_ncorr + k;
+        hipError_t e = ssf::launch_register((hipStream_t)stream, c->cfg, 1, a);
         if (e != hipSuccess) return hip_fail(c, e, "register_chain launch");
     }
     return SSF_OK;
@@ -650,13 +669,18 @@ int32_t ssf_register_batch_edges(ssf_ctx* c, void* stream, int32_t n_pairs,
                           d_last_edge_count, d_last_line, d_last_line_valid,
                           reinterpret_cast<const float4*>(d_curr_edge_xyzi), d_curr_edge_off,
                           d_curr_edge_count, max_edge_points, c->ecorr.as<ssf::CorrRec>(), d_ncorr_edge};
-    hipError_t e = ssf::launch_register(
-        (hipStream_t)stream, c->cfg, n_pairs, reinterpret_cast<const float4*>(d_last_xyzi), d_last_off,
-        d_last_count, d_last_normal, d_last_valid, reinterpret_cast<const float4*>(d_last_sorted_xyzi),
-        d_last_sorted_idx, reinterpret_cast<const float4*>(d_curr_xyzi), d_curr_off,
-        d_curr_count, max_plane_points, c->corr.as<ssf::CorrRec>(), d_pose_rel, d_pose_abs, d_log,
-        d_nlog, d_ncorr, nullptr, &er, reinterpret_cast<const float4*>(d_last_strip_xyzi),
-        d_last_strip_head);
+    ssf::RegisterArgs a{};                         // no 1-NN output, no compaction scratch
+    a.last.xyzi = reinterpret_cast<const float4*>(d_last_xyzi); a.last.off = d_last_off; a.last.count = d_last_count;
+    a.table.normal = d_last_normal; a.table.valid = d_last_valid;
+    a.table.sorted = reinterpret_cast<const float4*>(d_last_sorted_xyzi); a.table.sidx = d_last_sorted_idx;
+    a.table.strip_xyzi = reinterpret_cast<const float4*>(d_last_strip_xyzi); a.table.strip_head = d_last_strip_head;
+    a.curr.xyzi = reinterpret_cast<const float4*>(d_curr_xyzi); a.curr.off = d_curr_off; a.curr.count = d_curr_count;
+    a.pose.rel = d_pose_rel; a.pose.abs = d_pose_abs;
+    a.out.log = d_log; a.out.nlog = d_nlog; a.out.ncorr = d_ncorr;
+    a.scratch.corr = c->corr.as<ssf::CorrRec>();
+    a.max_m = max_plane_points;
+    a.edge = &er;
+    hipError_t e = ssf::launch_register((hipStream_t)stream, c->cfg, n_pairs, a);
     if (e != hipSuccess) return hip_fail(c, e, "register_edges launch");
     return SSF_OK;
 }

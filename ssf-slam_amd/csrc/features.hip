@@ -2159,41 +2159,38 @@ static size_t fix_head(int n_frames) { return ((size_t)n_frames * sizeof(uint32_
 size_t fix_bytes(int64_t total, int n_frames) { return fix_head(n_frames) + sizeof(int32_t) * (size_t)(total + 1); }
 
 hipError_t launch_extract_planes(hipStream_t s, const ssf_config& cfg, int n_frames,
-                                 const float* pts, int stride, const int64_t* frame_off,
-                                 int64_t max_pts, const uint8_t* keep, int8_t* rid, int32_t* hist,
-                                 int32_t* ring_off, int32_t* ring_idx, float4* ring_xyzi, float* curv,
-                                 uint8_t* flags, void* fix, int32_t* sel, float4* plane,
-                                 int32_t* plane_count, const EdgeSel* edge, const FeatScratch* fs) {
+                                 const FeatFrames& in, const FeatOut& out, int32_t* sel,
+                                 const BinScratch& bin, const FeatScratch& fs, const EdgeSel* edge) {
     const int R = cfg.n_rows;
-    const int n_chunks = (int)((max_pts + kBinChunk - 1) / kBinChunk);
+    const int n_chunks = (int)((in.max_pts + kBinChunk - 1) / kBinChunk);
     if (n_frames <= 0) return hipSuccess;
     if (R > kMaxRows) return hipErrorInvalidValue;
-    if (max_pts >= (int64_t)1 << 24) return hipErrorInvalidValue;   // ring positions: 24 bits
-    const bool dbg = curv != nullptr || ring_xyzi != nullptr;
+    if (in.max_pts >= (int64_t)1 << 24) return hipErrorInvalidValue;   // ring positions: 24 bits
+    const bool dbg = out.curv != nullptr || out.ring_xyzi != nullptr;
     const float emin = edge ? edge->min_curv : 0.f;
-    if (fs && feat_single_read(max_pts) && n_chunks > 0) {
+    if (feat_single_read(in.max_pts) && n_chunks > 0) {
         // the single-read stage: k_feat_chunk -> k_feat_select (-> k_feat_debug)
-        float* ccm = dbg ? fs->curv_cm : nullptr;
+        float* ccm = dbg ? fs.curv_cm : nullptr;
         const int64_t nblk = (int64_t)n_chunks * n_frames;
         const dim3 grid((unsigned)((nblk + 7) / 8 * 8));
         // unmasked 64-beam frames: the regular-window kernel first, then the general one for the
         // blocks it flagged (every other block returns at once)
-        const bool regular = !keep && R == kMaxRows && fs->irr && fs->lmap &&
-                             stride <= 4096;              // k_feat_wave_reg: 32-bit window offsets
+        const bool regular = !in.keep && R == kMaxRows && fs.irr && fs.lmap &&
+                             in.stride <= 4096;              // k_feat_wave_reg: 32-bit window offsets
         // the run kernel next, for the chunks k_feat_wave_reg left (every chunk when it did not
         // run: masked frames, 16 beams); then k_feat_chunk for the rest
-        const bool run = fs->irr && stride <= 4096;
-        uint8_t* irr = (regular || run) ? fs->irr : nullptr;
-        const RingTable* rt = reinterpret_cast<const RingTable*>(fs->rtab);
+        const bool run = fs.irr && in.stride <= 4096;
+        uint8_t* irr = (regular || run) ? fs.irr : nullptr;
+        const RingTable* rt = reinterpret_cast<const RingTable*>(fs.rtab);
         if (regular) {                                        // one wave per chunk
             kmark(s, "k_feat_wave_reg");
             const int64_t nwg = (nblk + kCurvNW - 1) / kCurvNW;
             const dim3 wgrid((unsigned)((nwg + 7) / 8 * 8));
 #define SSF_FR_LAUNCH(D, E)                                                                         \
-            hipLaunchKernelGGL((k_feat_wave_reg<D, E>), wgrid, dim3(kCurvNT), 0, s, pts, stride,     \
-                               frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
-                               cfg.plane_min, emin, rt, fs->cnt, fs->gidx, fs->gbits, ccm, irr,    \
-                               fs->lmap)
+            hipLaunchKernelGGL((k_feat_wave_reg<D, E>), wgrid, dim3(kCurvNT), 0, s, in.pts, in.stride, \
+                               in.frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
+                               cfg.plane_min, emin, rt, fs.cnt, fs.gidx, fs.gbits, ccm, irr,            \
+                               fs.lmap)
             if (edge) { if (dbg) SSF_FR_LAUNCH(true, true); else SSF_FR_LAUNCH(false, true); }
             else { if (dbg) SSF_FR_LAUNCH(true, false); else SSF_FR_LAUNCH(false, false); }
 #undef SSF_FR_LAUNCH
@@ -2203,16 +2200,16 @@ hipError_t launch_extract_planes(hipStream_t s, const ssf_config& cfg, int n_fra
             const int64_t nwg = (nblk + kCurvNW - 1) / kCurvNW;
             const dim3 wgrid((unsigned)((nwg + 7) / 8 * 8));
 #define SSF_RUN_LAUNCH(D, E)                                                                        \
-            hipLaunchKernelGGL((k_feat_wave_run<D, E>), wgrid, dim3(kCurvNT), 0, s, pts, stride,     \
-                               frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
-                               cfg.plane_min, emin, keep, rt, fs->cnt, fs->gidx, fs->gbits, ccm, irr, \
+            hipLaunchKernelGGL((k_feat_wave_run<D, E>), wgrid, dim3(kCurvNT), 0, s, in.pts, in.stride, \
+                               in.frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
+                               cfg.plane_min, emin, in.keep, rt, fs.cnt, fs.gidx, fs.gbits, ccm, irr,   \
                                regular ? 0 : 1)
             if (edge) { if (dbg) SSF_RUN_LAUNCH(true, true); else SSF_RUN_LAUNCH(false, true); }
             else { if (dbg) SSF_RUN_LAUNCH(true, false); else SSF_RUN_LAUNCH(false, false); }
 #undef SSF_RUN_LAUNCH
         }
-#define SSF_FC_COMMON pts, stride, frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
-                      cfg.plane_min, emin, keep, rt, fs->cnt, fs->gidx, fs->gbits, ccm
+#define SSF_FC_COMMON in.pts, in.stride, in.frame_off, n_frames, R, n_chunks, cfg.row_start,         \
+                      cfg.row_end, cfg.plane_min, emin, in.keep, rt, fs.cnt, fs.gidx, fs.gbits, ccm
         if (irr) {
             kmark(s, "k_feat_chunk_flagged");
             const dim3 fgrid((unsigned)((nblk + kFlagGroup - 1) / kFlagGroup));
@@ -2230,60 +2227,62 @@ hipError_t launch_extract_planes(hipStream_t s, const ssf_config& cfg, int n_fra
 #undef SSF_FC_COMMON
         kmark(s, "k_feat_select");
         if (edge)
-            hipLaunchKernelGGL(k_feat_select<true>, dim3(n_frames), dim3(kSelThreads), 0, s, pts, stride,
-                               frame_off, R, n_chunks, cfg.row_start, cfg.row_end, cfg.plane_span,
-                               cfg.plane_min, emin, fs->cnt, fs->gidx, fs->gbits, ring_off, ccm, sel,
-                               plane, plane_count, edge->span, edge->sel, edge->out, edge->count, irr,
-                               regular ? fs->lmap : nullptr);
+            hipLaunchKernelGGL(k_feat_select<true>, dim3(n_frames), dim3(kSelThreads), 0, s, in.pts,
+                               in.stride, in.frame_off, R, n_chunks, cfg.row_start, cfg.row_end, cfg.plane_span,
+                               cfg.plane_min, emin, fs.cnt, fs.gidx, fs.gbits, out.ring_off, ccm, sel,
+                               out.plane, out.plane_count, edge->span, edge->sel, edge->out, edge->count,
+                               irr, regular ? fs.lmap : nullptr);
         else
-            hipLaunchKernelGGL(k_feat_select<false>, dim3(n_frames), dim3(kSelThreads), 0, s, pts, stride,
-                               frame_off, R, n_chunks, cfg.row_start, cfg.row_end, cfg.plane_span,
-                               cfg.plane_min, emin, fs->cnt, fs->gidx, fs->gbits, ring_off, ccm, sel,
-                               plane, plane_count, 1, nullptr, nullptr, nullptr, irr,
-                               regular ? fs->lmap : nullptr);
+            hipLaunchKernelGGL(k_feat_select<false>, dim3(n_frames), dim3(kSelThreads), 0, s, in.pts,
+                               in.stride, in.frame_off, R, n_chunks, cfg.row_start, cfg.row_end, cfg.plane_span,
+                               cfg.plane_min, emin, fs.cnt, fs.gidx, fs.gbits, out.ring_off, ccm, sel,
+                               out.plane, out.plane_count, 1, nullptr, nullptr, nullptr, irr,
+                               regular ? fs.lmap : nullptr);
         if (dbg) {
             kmark(s, "k_feat_debug");
-            hipLaunchKernelGGL(k_feat_debug, dim3(n_chunks, n_frames), dim3(256), 0, s, pts, stride,
-                               frame_off, R, n_chunks, fs->cnt, ring_off, fs->gidx, fs->curv_cm,
-                               ring_xyzi, curv);
+            hipLaunchKernelGGL(k_feat_debug, dim3(n_chunks, n_frames), dim3(256), 0, s, in.pts, in.stride,
+                               in.frame_off, R, n_chunks, fs.cnt, out.ring_off, fs.gidx, fs.curv_cm,
+                               out.ring_xyzi, out.curv);
         }
         return hipGetLastError();
     }
     // fix-up lists: per-frame counts, then the entries at the frame offsets
-    uint32_t* fix_count = reinterpret_cast<uint32_t*>(fix);
-    int32_t* fixl = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(fix) + fix_head(n_frames));
+    uint32_t* fix_count = reinterpret_cast<uint32_t*>(bin.fix);
+    int32_t* fixl = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(bin.fix) + fix_head(n_frames));
     if (n_chunks > 0) {
         kmark(s, "k_bin_count");
-        if (!fs || !fs->rtab) return hipErrorInvalidValue;          // the ring-id table is required
-        hipLaunchKernelGGL(k_bin_count, dim3(n_chunks, n_frames), dim3(256), 0, s, pts, stride,
-                           frame_off, R, n_chunks, keep, reinterpret_cast<const RingTable*>(fs->rtab),
-                           rid, hist);
+        if (!fs.rtab) return hipErrorInvalidValue;                 // the ring-id table is required
+        hipLaunchKernelGGL(k_bin_count, dim3(n_chunks, n_frames), dim3(256), 0, s, in.pts, in.stride,
+                           in.frame_off, R, n_chunks, in.keep,
+                           reinterpret_cast<const RingTable*>(fs.rtab), bin.rid, bin.hist);
     }
     kmark(s, "k_bin_scan");
-    hipLaunchKernelGGL(k_bin_scan, dim3(n_frames), dim3(64), 0, s, R, n_chunks, hist, ring_off, fix_count);
+    hipLaunchKernelGGL(k_bin_scan, dim3(n_frames), dim3(64), 0, s, R, n_chunks, bin.hist,
+                       out.ring_off, fix_count);
     if (n_chunks > 0) {
         const int64_t nblk = (int64_t)((n_chunks + kCurvSub - 1) / kCurvSub) * n_frames;
         const dim3 grid((unsigned)((nblk + 7) / 8 * 8));
         kmark(s, "k_bin_curv");
 #define SSF_BC_LAUNCH(D, E)                                                                        \
-        hipLaunchKernelGGL((k_bin_curv<D, E>), grid, dim3(kCurvNT), 0, s, pts, stride, frame_off,       \
-                           n_frames, R, n_chunks, cfg.row_start, cfg.row_end, cfg.plane_min, emin,  \
-                           rid, hist, ring_off, ring_idx, flags, fixl, fix_count, ring_xyzi, curv)
+        hipLaunchKernelGGL((k_bin_curv<D, E>), grid, dim3(kCurvNT), 0, s, in.pts, in.stride,     \
+                           in.frame_off, n_frames, R, n_chunks, cfg.row_start, cfg.row_end,         \
+                           cfg.plane_min, emin, bin.rid, bin.hist, out.ring_off, bin.ring_idx,      \
+                           bin.flags, fixl, fix_count, out.ring_xyzi, out.curv)
         if (edge) { if (dbg) SSF_BC_LAUNCH(true, true); else SSF_BC_LAUNCH(false, true); }
         else { if (dbg) SSF_BC_LAUNCH(true, false); else SSF_BC_LAUNCH(false, false); }
 #undef SSF_BC_LAUNCH
     }
     kmark(s, "k_select");
     if (edge)
-        hipLaunchKernelGGL(k_select<true>, dim3(n_frames), dim3(kSelThreads), 0, s, pts, stride, frame_off,
-                           R, cfg.row_start, cfg.row_end, cfg.plane_span, cfg.plane_min, emin, ring_off,
-                           ring_idx, flags, fixl, fix_count, curv, sel, plane, plane_count, edge->span,
-                           edge->sel, edge->out, edge->count);
+        hipLaunchKernelGGL(k_select<true>, dim3(n_frames), dim3(kSelThreads), 0, s, in.pts, in.stride,
+                           in.frame_off, R, cfg.row_start, cfg.row_end, cfg.plane_span, cfg.plane_min,
+                           emin, out.ring_off, bin.ring_idx, bin.flags, fixl, fix_count, out.curv, sel,
+                           out.plane, out.plane_count, edge->span, edge->sel, edge->out, edge->count);
     else
-        hipLaunchKernelGGL(k_select<false>, dim3(n_frames), dim3(kSelThreads), 0, s, pts, stride, frame_off,
-                           R, cfg.row_start, cfg.row_end, cfg.plane_span, cfg.plane_min, emin, ring_off,
-                           ring_idx, flags, fixl, fix_count, curv, sel, plane, plane_count, 1, nullptr,
-                           nullptr, nullptr);
+        hipLaunchKernelGGL(k_select<false>, dim3(n_frames), dim3(kSelThreads), 0, s, in.pts, in.stride,
+                           in.frame_off, R, cfg.row_start, cfg.row_end, cfg.plane_span, cfg.plane_min,
+                           emin, out.ring_off, bin.ring_idx, bin.flags, fixl, fix_count, out.curv, sel,
+                           out.plane, out.plane_count, 1, nullptr, nullptr, nullptr);
     return hipGetLastError();
 }
 

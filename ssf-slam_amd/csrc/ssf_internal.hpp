@@ -92,15 +92,39 @@ bool feat_single_read(int64_t max_pts);
 // (ring_table_bytes); 0 or a negative code
 int build_ring_table(int n_rows, int chain, void* out_host);
 size_t ring_table_bytes();
+// Scratch that only the binning stage reads (k_bin_count / k_bin_scan / k_bin_curv / k_select,
+// frames beyond the single-read capacity).
+struct BinScratch {
+    int8_t* rid;        // ring id per input point (total bytes)
+    int32_t* hist;      // per (frame, chunk, row) counts
+    int32_t* ring_idx;  // input index per ring position (total)
+    uint8_t* flags;     // flag_bytes
+    void* fix;          // fix_bytes
+};
+// The input frames of launch_extract_planes (pts: stride floats per point, xyz first; keep: the
+// per-point mask, nullable) ...
+struct FeatFrames {
+    const float* pts;
+    int stride;
+    const int64_t* frame_off;
+    int64_t max_pts;
+    const uint8_t* keep;
+};
+// ... and its outputs: the plane clouds and per-frame counts, the ring offsets, and the debug
+// outputs (ring-ordered points and curvature, nullable).
+struct FeatOut {
+    float4* plane;
+    int32_t* plane_count;
+    int32_t* ring_off;
+    float4* ring_xyzi;
+    float* curv;
+};
+// sel: the per-row selection slots (total int32, ctx scratch); edge: nullptr = planes only.
 hipError_t launch_extract_planes(hipStream_t s, const ssf_config& cfg, int n_frames,
-                                 const float* pts, int stride, const int64_t* frame_off,
-                                 int64_t max_pts, const uint8_t* keep, int8_t* rid, int32_t* hist,
-                                 int32_t* ring_off, int32_t* ring_idx, float4* ring_xyzi,
-                                 float* curv, uint8_t* flags, void* fix, int32_t* sel, float4* plane,
-                                 int32_t* plane_count, const EdgeSel* edge = nullptr,
-                                 const FeatScratch* fs = nullptr);
+                                 const FeatFrames& in, const FeatOut& out, int32_t* sel,
+                                 const BinScratch& bin, const FeatScratch& fs, const EdgeSel* edge);
 
-// ---- launchers (registration.hip) ----
+// ---- launchers (plane_table.hip) ----
 hipError_t launch_plane_table(hipStream_t s, const ssf_config& cfg, int n_frames,
                               const float4* plane, const int64_t* frame_off, const int32_t* count,
                               int64_t max_m, float* normal, uint8_t* valid, float4* sorted_xyzi,
@@ -122,19 +146,51 @@ struct EdgeReg {
     CorrRec* corr;
     int32_t* ncorr;
 };
-hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, const float4* last,
-                           const int64_t* last_off, const int32_t* last_count,
-                           const float* last_normal, const uint8_t* last_valid,
-                           const float4* last_sorted, const int32_t* last_sidx, const float4* curr,
-                           const int64_t* curr_off, const int32_t* curr_count, int64_t max_m,
-                           CorrRec* corr, double* pose_rel, double* pose_abs, double* log,
-                           int32_t* nlog, int32_t* ncorr, int32_t* nn,
-                           const EdgeReg* edge = nullptr, const float4* last_strip_xyzi = nullptr,
-                           const int32_t* last_strip_head = nullptr, const double* pose_in = nullptr,
-                           const double* pose_abs_in = nullptr, int32_t* nnv = nullptr,
-                           int32_t* ncompact = nullptr);
-// (nnv [>= the current frames' total points] and ncompact [>= n_pairs]: scratch that lets the
-// lane-mode association hand the solve compacted records; nullptr = records in query order)
+// The arguments of launch_register.  A caller value-initialises a RegisterArgs and fills the
+// fields it has by name; a field left null is "not given".
+struct RegFrames {            // the pairs' last or current plane clouds
+    const float4* xyzi;
+    const int64_t* off;       // per pair
+    const int32_t* count;     // per pair
+};
+struct RegTable {             // the last frames' plane table (launch_plane_table's outputs)
+    const float* normal;
+    const uint8_t* valid;
+    const float4* sorted;     // x-sorted copy and permutation; null: brute-force association
+    const int32_t* sidx;
+    const float4* strip_xyzi; // the kept strip image; null: the association builds its strips
+    const int32_t* strip_head;
+};
+struct RegPoses {             // 7 doubles per pair (quaternion x, y, z, w, translation)
+    const double* in;         // warm starts; null: rel (in place)
+    const double* abs_in;     // start poses; null: abs (in place)
+    double* rel;
+    double* abs;              // nullable
+};
+struct RegOut {               // all nullable
+    double* log;
+    int32_t* nlog;
+    int32_t* ncorr;
+    int32_t* nn;
+};
+struct RegScratch {
+    CorrRec* corr;            // >= the current frames' total points
+    int32_t* nnv;             // >= the current frames' total points and
+    int32_t* ncompact;        // >= n_pairs: let the lane-mode association hand the solve
+                              // compacted records; null: records in query order
+};
+struct RegisterArgs {
+    RegFrames last;
+    RegTable table;
+    RegFrames curr;
+    RegPoses pose;
+    RegOut out;
+    RegScratch scratch;
+    int64_t max_m;            // bound of the plane points of any frame
+    const EdgeReg* edge;      // null: planes only
+};
+// association (associate.hip), then edge association (edges.hip), then the solve (solve.hip)
+hipError_t launch_register(hipStream_t s, const ssf_config& cfg, int n_pairs, const RegisterArgs& a);
 // What launch_register launches for the association of n_pairs pairs bounded by max_m plane
 // points, given the sorted buffers (and, for `compacted`, the nnv / ncompact scratch): host
 // arithmetic only.  strips = false: not the k_associate_strips path, the other fields are 0.
@@ -147,6 +203,13 @@ struct RegisterPlan {
     int lds_cap;      // last-frame points staged in LDS (a longer last frame walks global memory)
 };
 RegisterPlan register_plan(int n_pairs, int64_t max_m, bool with_edges);
+// launch_register's three stages, each beside its kernels (pin / ain: the resolved warm starts
+// and start poses; ncp: the compacted-record counts or null); launch_register checks for errors
+void launch_associate(hipStream_t s, int n_pairs, const RegisterPlan& plan, const RegisterArgs& a,
+                      const double* pin);
+void launch_edge_associate(hipStream_t s, int n_pairs, const EdgeReg* edge, const double* pin);
+void launch_solve(hipStream_t s, const ssf_config& cfg, int n_pairs, const RegisterArgs& a,
+                  const double* pin, const double* ain, int32_t* ncp);
 hipError_t launch_edge_table(hipStream_t s, const ssf_edge_config& ec, int n_frames,
                              const float4* edges, const int64_t* frame_off, const int32_t* count,
                              int64_t max_m, float* line, uint8_t* valid);

@@ -22,7 +22,7 @@ MASK_GMM, MASK_GT, MASK_GIVEN = 0, 1, 2
 RING_CHAIN_FLOAT, RING_CHAIN_DOUBLE = 0, 1
 RING_CHAINS = {"float": RING_CHAIN_FLOAT, "double": RING_CHAIN_DOUBLE}
 # frames of plane points the association can stage from the plane table's strip image
-# (registration.hip: kStripHeadWords, kAssocStripF4Max)
+# (reg_strips.hpp: kStripHeadWords, kAssocStripF4Max)
 STRIP_IMAGE_MIN, STRIP_IMAGE_MAX = (256 + 1) + 2 * 256 + 4, 6144
 POSE_OUT_STRIDE = 32
 POSE_OUT = dict(T=0, Q=3, R=7, STATUS=16, NBG=17, BGLABEL=18, KM_ITER=19, EM_ITER=20,

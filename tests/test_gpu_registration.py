@@ -610,7 +610,7 @@ def test_plane_table_split_over_work_groups(oracle, dev):
                sx[o:o + m].cpu().numpy(), si[o:o + m].cpu().numpy()]
         if tab.strips is not None:                            # the image and its defined head words
             img, head = (t[o:o + m].cpu().numpy() for t in tab.strips)
-            K = 256                                           # kStripMax (registration.hip)
+            K = 256                                           # kStripMax (reg_strips.hpp)
             ns = int(head[3 * K + 4]) & 0xFFFF
             got += [img, head[:K + 1], head[K + 1:K + 1 + ns], head[2 * K + 1:2 * K + 1 + ns],
                     head[3 * K + 1:3 * K + 5]]
