@@ -14,6 +14,16 @@
  *     features are [B, C, N] float32; indices are int32.
  *   - Return 0 on success, <0 on error; ssf_pn2_last_error() describes the calling thread's
  *     last error.  Indices outside their range read as 0 and set *d_bad (device int32) to 1.
+ *
+ * Entry point                     replaces (scripts/ActiveSceneFlow)
+ *   ssf_pn2_furthest_point_sample pointutils.furthest_point_sample        utils/utils.py:226
+ *   ssf_pn2_knn / _three_nn       pointutils.knn / three_nn               utils/utils.py:229,560
+ *   ssf_pn2_gather                pointutils.gather_ / grouping_operation utils/utils.py:228,231
+ *   ssf_pn2_group_relative        the grouping block of a set abstraction utils/utils.py:228-234
+ *   ssf_pn2_three_interpolate     pointutils.three_interpolate            utils/utils.py:658-663
+ *   ssf_pn2_upsample_flow         UpsampleFlow.forward                    utils/soflow.py:1442-1470
+ *   ssf_pn2_grouped_mlp_max       grouping + mlp + max of PointNetSetAbstraction (utils.py:231-247)
+ *                                 and of PointNetSetUpConv's mlp1 (utils.py:296-307), one kernel
  */
 #ifndef SSF_POINTNET2_H
 #define SSF_POINTNET2_H
@@ -27,6 +37,8 @@ extern "C" {
 #define SSF_PN2_E_HIP (-2)
 #define SSF_PN2_KNN_MAX 32
 #define SSF_PN2_UPSAMPLE_MAX_SPARSE 4096
+#define SSF_PN2_MLP_MAX_LAYERS 3
+#define SSF_PN2_MLP_MAX_WIDTH 512
 
 const char* ssf_pn2_last_error(void);
 
@@ -66,6 +78,28 @@ int32_t ssf_pn2_gather(void* stream, int32_t b, int32_t c, int32_t n, int32_t g,
 int32_t ssf_pn2_group_relative(void* stream, int32_t b, int32_t n, int32_t s, int32_t k, int32_t c,
                                const float* d_xyz, const float* d_new_xyz, const float* d_feat,
                                const int32_t* d_idx, float* d_out, int32_t* d_bad);
+
+/* The grouping block above, the shared mlp and the max over the k samples of
+ * PointNetSetAbstraction.forward (utils/utils.py:231-247) in one kernel, with no [b, C, s, k]
+ * tensor in memory.  Per centroid j and sample m the input column is
+ * cat(xyz[:, idx[j, m]] - new_xyz[:, j], feat[:, idx[j, m]]) (3 + c channels, the order of
+ * :232-234); layer l computes y[o] = max(0, fmaf(sum_i wt[i][o] x[i], scale[o], shift[o])) -- a
+ * bias-free 1x1 convolution (sum over i ascending, an f32 fma chain), eval-mode BatchNorm folded
+ * into scale and shift by the caller, ReLU -- and d_out [b, widths[n_layers], s] is the max over
+ * the k samples of the last layer.
+ *   d_xyz [b, 3, n] (n <= 36864), d_new_xyz [b, 3, s], d_feat [b, c, n] (nullable when c = 0),
+ *   d_idx [b, s, k] (1 <= k <= SSF_PN2_KNN_MAX);
+ *   widths: HOST array of n_layers + 1 ints (1 <= n_layers <= SSF_PN2_MLP_MAX_LAYERS, every
+ *   width in [1, SSF_PN2_MLP_MAX_WIDTH], widths[0] = 3 + c);
+ *   d_wt / d_scale / d_shift: HOST arrays of n_layers DEVICE pointers; layer l's weights are
+ *   [widths[l], widths[l + 1]] (input-major), its scale and shift [widths[l + 1]].
+ * Writes exactly b * widths[n_layers] * s floats, allocates nothing, launches one kernel; a
+ * batch element's output does not depend on the rest of the batch. */
+int32_t ssf_pn2_grouped_mlp_max(void* stream, int32_t b, int32_t n, int32_t s, int32_t k, int32_t c,
+                                const float* d_xyz, const float* d_new_xyz, const float* d_feat,
+                                const int32_t* d_idx, int32_t n_layers, const int32_t* widths,
+                                const float* const* d_wt, const float* const* d_scale,
+                                const float* const* d_shift, float* d_out, int32_t* d_bad);
 
 /* pointutils.three_interpolate(features [b, c, m], idx [b, n, 3], weight [b, n, 3]) ->
  * [b, c, n]: w0 f[i0] + w1 f[i1] + w2 f[i2] (the weighted 3-NN sum of

@@ -11,11 +11,14 @@
 //   three_interpolate      <- the weighted 3-NN sum   utils/utils.py:658-663
 //   upsample_flow (fused)  <- UpsampleFlow.forward    utils/soflow.py:1442-1470
 //   group_relative (fused) <- the grouping block of PointNetSetAbstraction.forward, utils.py:228-234
+//   grouped_mlp_max (fused) <- grouping + mlp + max of PointNetSetAbstraction.forward, utils.py:231-247,
+//                              and of PointNetSetUpConv.forward's mlp1, utils.py:296-307
 //
 // Kernels (DESIGN.md §5 has their measured rates): k_fps_pk / k_fps (one work-group per cloud,
 // packed-f32 distances, DPP wave reductions), k_knn / k_knn_split (brute-force exact k-NN over
 // LDS tiles; the split variant spreads one cloud's reference set over 8 waves), k_gather_lds /
-// k_three_interp_lds (feature rows staged in LDS) with global fallbacks, k_upsample (fused).
+// k_three_interp_lds (feature rows staged in LDS) with global fallbacks, k_upsample (fused),
+// k_grouped_mlp_max (f32 MFMA over LDS-resident activations).
 //
 // Layouts are the extension's: coordinates [B, N, 3] ("xyz_t"), features [B, C, N], indices
 // int32.  Every entry point is stateless and asynchronous on the caller's stream.
@@ -542,6 +545,177 @@ __global__ __launch_bounds__(TPB) void k_upsample(const float* __restrict__ xyz,
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// grouped_mlp_max: the body of PointNetSetAbstraction.forward after the k-NN (utils.py:231-247)
+// and of PointNetSetUpConv.forward's mlp1 (utils.py:296-307) in one kernel -- gather, relative
+// coordinates, up to three (1x1 conv, folded BatchNorm, ReLU) layers and the max over the k
+// samples.  A work-group owns TC columns (32-column tiles of 32 / k whole centroids each, so no
+// centroid straddles an MFMA tile; unused columns are zero) laid out in LDS as
+// [channel][column].  Layer l reads buffer l & 1 and writes the other one; each of the eight
+// waves takes (32 output channels) x (32 columns) tiles and runs v_mfma_f32_32x32x2_f32 over the
+// input channels in ascending order (an exact f32 fma chain, so a fixed summation order).  A =
+// the input-major weights (lane = output channel: contiguous loads), B = the LDS activations
+// (lane = column).  The last layer's tile goes through a per-wave 32 x 33 staging patch in the
+// free buffer for the max over k and straight to d_out.  Rows and channels past a width are
+// fed as zeros by clamped loads and selects; the caller's arrays are never read past their end.
+constexpr int kMlpThreads = 512;
+constexpr int kMlpWaves = kMlpThreads / 64;
+constexpr int kMlpStage = 32 * 33;             // floats per wave of last-layer staging
+constexpr int kMlpLdsMax = 160 * 1024;
+constexpr int kMlpUnroll = 8;                  // MFMA k-steps whose operands are loaded together
+
+typedef float f16v __attribute__((ext_vector_type(16)));
+
+struct MlpArgs {
+    const float* xyz;
+    const float* new_xyz;
+    const float* feat;
+    const int32_t* idx;
+    const float* wt[SSF_PN2_MLP_MAX_LAYERS];
+    const float* scale[SSF_PN2_MLP_MAX_LAYERS];
+    const float* shift[SSF_PN2_MLP_MAX_LAYERS];
+    float* out;
+    int32_t* bad;
+    int32_t width[SSF_PN2_MLP_MAX_LAYERS + 1];
+    int32_t n, s, k, c, n_layers, tc, buf1;    // buf1: float offset of the second LDS buffer
+};
+
+extern __shared__ float mlp_lds[];
+
+// acc = W[:, o0 .. o0 + 32)^T X[:, c0 .. c0 + 32) over the w_in input channels, k ascending; X is
+// the [channel][tc] image at float offset x0 of the work-group's LDS
+SSF_DEV f16v mlp_tile(const float* __restrict__ W, int w_in, int w_out, int o0, int x0, int tc,
+                      int c0, int lane) {
+    const int r = lane & 31, h = lane >> 5;
+    const int o = o0 + r;
+    const bool ov = o < w_out;
+    const unsigned wc = ov ? o : w_out - 1, xc = x0 + c0 + r;     // 32-bit offsets from uniform bases
+    f16v acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+    // operands of kMlpUnroll k-steps from input channel k0 on.  issue() only loads, from rows
+    // clamped into the arrays; settle() zeroes what lies past a width just before the MFMAs.  The
+    // empty asm pins each load ahead of its select, so the loads stay unconditional and in flight
+    // together instead of sinking into one branch (and one wait) each.
+    auto issue = [&](int k0, float (&a)[kMlpUnroll], float (&b)[kMlpUnroll]) {
+#pragma unroll
+        for (int u = 0; u < kMlpUnroll; ++u) {
+            const int kr = k0 + 2 * u + h;
+            const unsigned kc = kr < w_in ? kr : w_in - 1;
+            a[u] = W[kc * w_out + wc];
+            b[u] = mlp_lds[kc * tc + xc];
+        }
+    };
+    auto settle = [&](int k0, float (&a)[kMlpUnroll], float (&b)[kMlpUnroll]) {
+#pragma unroll
+        for (int u = 0; u < kMlpUnroll; ++u) asm volatile("" : "+v"(a[u]), "+v"(b[u]));
+#pragma unroll
+        for (int u = 0; u < kMlpUnroll; ++u) {
+            const bool kv = k0 + 2 * u + h < w_in;
+            a[u] = (kv && ov) ? a[u] : 0.0f;
+            b[u] = kv ? b[u] : 0.0f;
+        }
+    };
+    auto mma = [&](const float (&a)[kMlpUnroll], const float (&b)[kMlpUnroll]) {
+#pragma unroll
+        for (int u = 0; u < kMlpUnroll; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+    };
+    // two register sets: the loads of one group of k-steps are in flight under the MFMAs of the
+    // group before it (the weights come from L2 or beyond)
+    constexpr int kStep = 2 * kMlpUnroll;
+    float a0[kMlpUnroll], b0[kMlpUnroll], a1[kMlpUnroll], b1[kMlpUnroll];
+    issue(0, a0, b0);
+#pragma nounroll
+    for (int k0 = 0; k0 < w_in; k0 += 2 * kStep) {
+        issue(k0 + kStep, a1, b1);
+        settle(k0, a0, b0);
+        mma(a0, b0);
+        issue(k0 + 2 * kStep, a0, b0);
+        settle(k0 + kStep, a1, b1);
+        if (k0 + kStep < w_in) mma(a1, b1);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(kMlpThreads) void k_grouped_mlp_max(const MlpArgs A) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, tc = A.tc, k = A.k, n = A.n, s = A.s;
+    const int cpt = 32 / k, ct = tc >> 5;                      // centroids per tile, tiles
+    const int j0 = blockIdx.x * (cpt * ct);                    // first centroid of the block
+    int32_t* sidx = reinterpret_cast<int32_t*>(mlp_lds) + (A.buf1 - 2 * tc);   // [tc] index, [tc] centroid
+
+    // the block's index list: -1 marks an unused column
+    for (int col = tid; col < tc; col += kMlpThreads) {
+        const int t = col >> 5, w = col & 31, q = w / k, m = w - q * k;
+        const int j = j0 + t * cpt + q;
+        int i = -1;
+        if (q < cpt && j < s) {
+            i = A.idx[((int64_t)b * s + j) * k + m];
+            if ((unsigned)i >= (unsigned)n) { *A.bad = 1; i = 0; }
+        }
+        sidx[col] = i;
+        sidx[tc + col] = j;
+    }
+    __syncthreads();
+    // input columns: cat(xyz[:, i] - new_xyz[:, j], feat[:, i])  (utils.py:232-234)
+    const int w0 = A.width[0];
+    const float* XY = A.xyz + (int64_t)b * 3 * n;
+    const float* NX = A.new_xyz + (int64_t)b * 3 * s;
+    const float* FT = A.feat ? A.feat + (int64_t)b * A.c * n : nullptr;
+    for (int e = tid; e < w0 * tc; e += kMlpThreads) {
+        const int ch = e / tc, col = e - ch * tc;
+        const int i = sidx[col];
+        float v = 0.0f;
+        if (i >= 0) v = ch < 3 ? XY[ch * n + i] - NX[ch * s + sidx[tc + col]] : FT[(int64_t)(ch - 3) * n + i];
+        mlp_lds[e] = v;
+    }
+    __syncthreads();
+
+    const int r = lane & 31, h = lane >> 5;
+    for (int l = 0; l < A.n_layers; ++l) {
+        const int w_in = A.width[l], w_out = A.width[l + 1];
+        const int x0 = (l & 1) ? A.buf1 : 0, y0 = (l & 1) ? 0 : A.buf1;
+        const bool last = l + 1 == A.n_layers;
+        const int ot = (w_out + 31) >> 5;
+        const int st0 = y0 + wave * kMlpStage;                 // the wave's staging patch
+        const float* __restrict__ SC = A.scale[l];
+        const float* __restrict__ SH = A.shift[l];
+        for (int p = wave; p < ot * ct; p += kMlpWaves) {
+            const int o0 = (p / ct) << 5, c0 = (p % ct) << 5;
+            const f16v acc = mlp_tile(A.wt[l], w_in, w_out, o0, x0, tc, c0, lane);
+            // C/D map of the 32x32 MFMA: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+                const int o = o0 + row;
+                const int oc = o < w_out ? o : w_out - 1;
+                const float y = fmaxf(0.0f, __builtin_fmaf(acc[i], SC[oc], SH[oc]));
+                if (last) mlp_lds[st0 + row * 33 + r] = y;
+                else if (o < w_out) mlp_lds[y0 + o * tc + c0 + r] = y;
+            }
+            if (last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                // torch.max(new_points, -1)[0] (utils.py:247): 32 rows x cpt centroids of this tile
+                const int jt = j0 + (c0 >> 5) * cpt;
+                for (int e = lane; e < 32 * cpt; e += 64) {
+                    const int row = e / cpt, q = e - row * cpt;
+                    const int o = o0 + row, j = jt + q;
+                    if (o < w_out && j < s) {
+                        const int s0 = st0 + row * 33 + q * k;
+                        float mx = mlp_lds[s0];
+                        for (int m = 1; m < k; ++m) mx = fmaxf(mx, mlp_lds[s0 + m]);
+                        A.out[((int64_t)b * w_out + o) * s + j] = mx;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // The LDS-staged kernels take up to 144 KiB of dynamic LDS (above the 64 KiB default limit).
 hipError_t allow_stage_lds() {
     static hipError_t once = [] {
@@ -662,6 +836,56 @@ int32_t ssf_pn2_group_relative(void* stream, int32_t b, int32_t n, int32_t s, in
                            d_feat, c, n, d_idx, g, ch, d_out, oc, 3, (const float*)nullptr, 1, d_bad);
     }
     return hip_status(hipGetLastError(), "k_gather_lds (features)");
+}
+
+int32_t ssf_pn2_grouped_mlp_max(void* stream, int32_t b, int32_t n, int32_t s, int32_t k, int32_t c,
+                                const float* d_xyz, const float* d_new_xyz, const float* d_feat,
+                                const int32_t* d_idx, int32_t n_layers, const int32_t* widths,
+                                const float* const* d_wt, const float* const* d_scale,
+                                const float* const* d_shift, float* d_out, int32_t* d_bad) {
+    if (b < 0 || b > 65535 || n <= 0 || n > kStageFloats || s < 0 || k <= 0 || k > SSF_PN2_KNN_MAX || c < 0)
+        return fail(SSF_PN2_E_ARG, "grouped_mlp_max: bad arguments (0 <= b <= 65535, 0 < n <= 36864, s >= 0, 0 < k <= 32)");
+    if (n_layers < 1 || n_layers > SSF_PN2_MLP_MAX_LAYERS)
+        return fail(SSF_PN2_E_ARG, "grouped_mlp_max: need 1 <= n_layers <= 3");
+    if (!d_xyz || !d_new_xyz || (c > 0 && !d_feat) || !d_idx || !widths || !d_wt || !d_scale || !d_shift ||
+        !d_out || !d_bad)
+        return fail(SSF_PN2_E_ARG, "grouped_mlp_max: null pointer");
+    MlpArgs a{};
+    for (int l = 0; l <= n_layers; ++l) {
+        if (widths[l] < 1 || widths[l] > SSF_PN2_MLP_MAX_WIDTH)
+            return fail(SSF_PN2_E_ARG, "grouped_mlp_max: every width must be in [1, 512]");
+        a.width[l] = widths[l];
+    }
+    if ((int64_t)widths[0] != (int64_t)3 + c) return fail(SSF_PN2_E_ARG, "grouped_mlp_max: widths[0] != 3 + c");
+    for (int l = 0; l < n_layers; ++l) {
+        if (!d_wt[l] || !d_scale[l] || !d_shift[l]) return fail(SSF_PN2_E_ARG, "grouped_mlp_max: null layer pointer");
+        a.wt[l] = d_wt[l]; a.scale[l] = d_scale[l]; a.shift[l] = d_shift[l];
+    }
+    if (b == 0 || s == 0) return SSF_PN2_OK;
+    // LDS rows of the two ping-pong buffers: layer l reads buffer l & 1
+    int rows[2] = {0, 0};
+    for (int l = 0; l < n_layers; ++l) rows[l & 1] = max(rows[l & 1], widths[l]);
+    // the widest column tile (128, 64 or 32 columns) whose LDS lets two work-groups share a CU;
+    // 32 columns always fit (two 512-row buffers: 128 KiB)
+    int tc = 128, buf1 = 0;
+    size_t bytes = 0;
+    for (;; tc >>= 1) {
+        int f[2] = {rows[0] * tc, rows[1] * tc};
+        f[n_layers & 1] = max(f[n_layers & 1], kMlpWaves * kMlpStage);
+        buf1 = f[0] + 2 * tc;
+        bytes = ((size_t)buf1 + f[1]) * 4;
+        if (bytes <= (size_t)kMlpLdsMax / 2 || tc == 32) break;
+    }
+    if (bytes > (size_t)kMlpLdsMax) return fail(SSF_PN2_E_ARG, "grouped_mlp_max: widths do not fit in LDS");
+    static hipError_t once = hipFuncSetAttribute((const void*)k_grouped_mlp_max,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsMax);
+    if (once != hipSuccess) return hip_status(once, "grouped_mlp_max: LDS limit");
+    a.xyz = d_xyz; a.new_xyz = d_new_xyz; a.feat = d_feat; a.idx = d_idx; a.out = d_out; a.bad = d_bad;
+    a.n = n; a.s = s; a.k = k; a.c = c; a.n_layers = n_layers; a.tc = tc; a.buf1 = buf1;
+    const int cpb = (32 / k) * (tc / 32);
+    hipLaunchKernelGGL(k_grouped_mlp_max, dim3((s + cpb - 1) / cpb, b), dim3(kMlpThreads), bytes,
+                       (hipStream_t)stream, a);
+    return hip_status(hipGetLastError(), "k_grouped_mlp_max");
 }
 
 int32_t ssf_pn2_three_interpolate(void* stream, int32_t b, int32_t c, int32_t m, int32_t n,
