@@ -24,6 +24,11 @@
  *   ssf_pn2_upsample_flow         UpsampleFlow.forward                    utils/soflow.py:1442-1470
  *   ssf_pn2_grouped_mlp_max       grouping + mlp + max of PointNetSetAbstraction (utils.py:231-247)
  *                                 and of PointNetSetUpConv's mlp1 (utils.py:296-307), one kernel
+ *   ssf_pn2_grouped_mlp           the grouped MLPs of PointConvTransFlowV2 (mlp_convs .. mlp_convs4,
+ *                                 weightnet1)                              utils/soflow.py:392-509
+ *   ssf_pn2_pair_attention        the k x k mutual attention of a cost volume utils/soflow.py:420-458
+ *   ssf_pn2_segment_softmax_sum   softmax-weighted sums, by centroid or by scatter target
+ *                                 (torch_scatter's scatter_softmax, scatter_sum) utils/soflow.py:469-486
  */
 #ifndef SSF_POINTNET2_H
 #define SSF_POINTNET2_H
@@ -39,6 +44,8 @@ extern "C" {
 #define SSF_PN2_UPSAMPLE_MAX_SPARSE 4096
 #define SSF_PN2_MLP_MAX_LAYERS 3
 #define SSF_PN2_MLP_MAX_WIDTH 512
+#define SSF_PN2_GMLP_MAX_IN 766
+#define SSF_PN2_ATTN_MAX_C 512
 
 const char* ssf_pn2_last_error(void);
 
@@ -100,6 +107,60 @@ int32_t ssf_pn2_grouped_mlp_max(void* stream, int32_t b, int32_t n, int32_t s, i
                                 const int32_t* d_idx, int32_t n_layers, const int32_t* widths,
                                 const float* const* d_wt, const float* const* d_scale,
                                 const float* const* d_shift, float* d_out, int32_t* d_bad);
+
+/* The grouped MLP above, generalised for the cost volume of PointConvTransFlowV2
+ * (utils/soflow.py:392-509).  Per centroid j and sample m the input column is the concatenation,
+ * in this order, of up to four segments (a segment with a null pointer / zero width is absent):
+ *   1. d_ctr [b, c_ctr, s]:        ctr[:, j], one value per centroid, the same for every m;
+ *   2. d_feat [b, c_g, n]:         feat[:, idx[j, m]];
+ *   3. d_dense [b, c_d, s, k]:     dense[:, j, m];
+ *   4. d_xyz [b, 3, n] with d_new_xyz [b, 3, s]:  xyz[:, idx[j, m]] - new_xyz[:, j] (3 channels).
+ * Layer l computes t = fmaf(sum_i wt[i][o] x[i], scale[o], shift[o]) (i ascending, an f32 fma
+ * chain) and y = t > 0 ? t : slope[l] * t: slope 0 is ReLU, 0.1 the reference's LeakyReLU, 1 no
+ * activation.  A convolution bias is scale = 1, shift = bias.
+ *   d_idx [b, s, k] is needed (with 0 < n <= 36864) when segment 2 or 4 is present, else nullable;
+ *   widths: HOST array of n_layers + 1 ints, 1 <= n_layers <= SSF_PN2_MLP_MAX_LAYERS;
+ *   widths[0] = c_ctr + c_g + c_d + (d_xyz ? 3 : 0), in [1, SSF_PN2_GMLP_MAX_IN]; every other
+ *   width in [1, SSF_PN2_MLP_MAX_WIDTH].  766 input rows are what two LDS images of a 32-column
+ *   tile leave beside a 512-row second image: (766 * 32 + 64 + 512 * 32) * 4 B = 160 KiB;
+ *   d_wt / d_scale / d_shift: HOST arrays of n_layers DEVICE pointers, as for grouped_mlp_max;
+ *   slope: HOST array of n_layers floats;  1 <= k <= SSF_PN2_KNN_MAX.
+ * full_output = 0: d_out [b, widths[n_layers], s], the max over the k samples;
+ * full_output = 1: d_out [b, widths[n_layers], s, k], every column.
+ * Writes exactly that many floats, allocates nothing, launches one kernel; a batch element's
+ * output does not depend on the rest of the batch and is the same from run to run. */
+int32_t ssf_pn2_grouped_mlp(void* stream, int32_t b, int32_t n, int32_t s, int32_t k, int32_t c_ctr,
+                            int32_t c_g, int32_t c_d, const float* d_ctr, const float* d_feat,
+                            const float* d_dense, const float* d_xyz, const float* d_new_xyz,
+                            const int32_t* d_idx, int32_t n_layers, const int32_t* widths,
+                            const float* const* d_wt, const float* const* d_scale,
+                            const float* const* d_shift, const float* slope, int32_t full_output,
+                            float* d_out, int32_t* d_bad);
+
+/* The mutual attention between the two grouped feature sets of a cost volume
+ * (utils/soflow.py:420-458), one launch.  d_q, d_kw [b, c, s, k] -> d_qm, d_kwm [b, c, s, k].  Per
+ * centroid: a[m][m'] = sum_ch q[ch][m] kw[ch][m'] (ch ascending, fma chain; no 1 / sqrt(c)),
+ * W = softmax over m of a (times) softmax over m' of a, with expf on max-subtracted arguments,
+ *   qm[ch][m]   = q[ch][m]   + sum_m' W[m][m'] kw[ch][m'],
+ *   kwm[ch][m'] = kw[ch][m'] + sum_m  q[ch][m] W[m][m'],   both sums ascending.
+ * 1 <= c <= SSF_PN2_ATTN_MAX_C, 1 <= k <= SSF_PN2_KNN_MAX.  The outputs must not alias the inputs. */
+int32_t ssf_pn2_pair_attention(void* stream, int32_t b, int32_t c, int32_t s, int32_t k,
+                               const float* d_q, const float* d_kw, float* d_qm, float* d_kwm);
+
+/* Softmax-weighted sums over segments of a flat entry list (utils/soflow.py:469-486).
+ * d_logit [b, m], d_val [b, c, m] -> d_out [b, c, t_n]:
+ *   out[ch][t] = sum_e w_e val[ch][e],  w_e = expf(l_e - max_seg) / sum_seg expf(l - max_seg),
+ * over the entries e of segment t, in the segment's order (fma chain); an empty segment gives 0.
+ *   uniform segments: d_offsets = d_order = NULL and m = t_n * k: segment t = entries
+ *     [t k, (t + 1) k) (weights1 and point_to_patch_cost_fwd, :469,:486);
+ *   CSR segments: d_offsets [b, t_n + 1] (ascending, within [0, m]) and d_order [b, m], the entries
+ *     grouped by segment (scatter_softmax, the product and scatter_sum of :474-481); k is ignored.
+ * An entry of d_order outside [0, m) reads as entry 0, an offset outside [0, m] or below its
+ * predecessor is clamped, and either sets *d_bad.  Segments may have any length. */
+int32_t ssf_pn2_segment_softmax_sum(void* stream, int32_t b, int32_t c, int32_t m, int32_t t_n,
+                                    int32_t k, const float* d_logit, const float* d_val,
+                                    const int32_t* d_offsets, const int32_t* d_order, float* d_out,
+                                    int32_t* d_bad);
 
 /* pointutils.three_interpolate(features [b, c, m], idx [b, n, 3], weight [b, n, 3]) ->
  * [b, c, n]: w0 f[i0] + w1 f[i1] + w2 f[i2] (the weighted 3-NN sum of

@@ -30,6 +30,7 @@
 #include <cstring>
 
 #include "ssf_device.hpp"
+#include "mlp_tile.hpp"
 #include "../../include/ssf_pointnet2.h"
 
 namespace {
@@ -558,14 +559,7 @@ __global__ __launch_bounds__(TPB) void k_upsample(const float* __restrict__ xyz,
 // (lane = column).  The last layer's tile goes through a per-wave 32 x 33 staging patch in the
 // free buffer for the max over k and straight to d_out.  Rows and channels past a width are
 // fed as zeros by clamped loads and selects; the caller's arrays are never read past their end.
-constexpr int kMlpThreads = 512;
-constexpr int kMlpWaves = kMlpThreads / 64;
-constexpr int kMlpStage = 32 * 33;             // floats per wave of last-layer staging
-constexpr int kMlpLdsMax = 160 * 1024;
-constexpr int kMlpUnroll = 8;                  // MFMA k-steps whose operands are loaded together
-
-typedef float f16v __attribute__((ext_vector_type(16)));
-
+// The tile (mlp_tile) and its constants are in mlp_tile.hpp, shared with cost_volume.hip.
 struct MlpArgs {
     const float* xyz;
     const float* new_xyz;
@@ -579,63 +573,6 @@ struct MlpArgs {
     int32_t width[SSF_PN2_MLP_MAX_LAYERS + 1];
     int32_t n, s, k, c, n_layers, tc, buf1;    // buf1: float offset of the second LDS buffer
 };
-
-extern __shared__ float mlp_lds[];
-
-// acc = W[:, o0 .. o0 + 32)^T X[:, c0 .. c0 + 32) over the w_in input channels, k ascending; X is
-// the [channel][tc] image at float offset x0 of the work-group's LDS
-SSF_DEV f16v mlp_tile(const float* __restrict__ W, int w_in, int w_out, int o0, int x0, int tc,
-                      int c0, int lane) {
-    const int r = lane & 31, h = lane >> 5;
-    const int o = o0 + r;
-    const bool ov = o < w_out;
-    const unsigned wc = ov ? o : w_out - 1, xc = x0 + c0 + r;     // 32-bit offsets from uniform bases
-    f16v acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-    // operands of kMlpUnroll k-steps from input channel k0 on.  issue() only loads, from rows
-    // clamped into the arrays; settle() zeroes what lies past a width just before the MFMAs.  The
-    // empty asm pins each load ahead of its select, so the loads stay unconditional and in flight
-    // together instead of sinking into one branch (and one wait) each.
-    auto issue = [&](int k0, float (&a)[kMlpUnroll], float (&b)[kMlpUnroll]) {
-#pragma unroll
-        for (int u = 0; u < kMlpUnroll; ++u) {
-            const int kr = k0 + 2 * u + h;
-            const unsigned kc = kr < w_in ? kr : w_in - 1;
-            a[u] = W[kc * w_out + wc];
-            b[u] = mlp_lds[kc * tc + xc];
-        }
-    };
-    auto settle = [&](int k0, float (&a)[kMlpUnroll], float (&b)[kMlpUnroll]) {
-#pragma unroll
-        for (int u = 0; u < kMlpUnroll; ++u) asm volatile("" : "+v"(a[u]), "+v"(b[u]));
-#pragma unroll
-        for (int u = 0; u < kMlpUnroll; ++u) {
-            const bool kv = k0 + 2 * u + h < w_in;
-            a[u] = (kv && ov) ? a[u] : 0.0f;
-            b[u] = kv ? b[u] : 0.0f;
-        }
-    };
-    auto mma = [&](const float (&a)[kMlpUnroll], const float (&b)[kMlpUnroll]) {
-#pragma unroll
-        for (int u = 0; u < kMlpUnroll; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
-    };
-    // two register sets: the loads of one group of k-steps are in flight under the MFMAs of the
-    // group before it (the weights come from L2 or beyond)
-    constexpr int kStep = 2 * kMlpUnroll;
-    float a0[kMlpUnroll], b0[kMlpUnroll], a1[kMlpUnroll], b1[kMlpUnroll];
-    issue(0, a0, b0);
-#pragma nounroll
-    for (int k0 = 0; k0 < w_in; k0 += 2 * kStep) {
-        issue(k0 + kStep, a1, b1);
-        settle(k0, a0, b0);
-        mma(a0, b0);
-        issue(k0 + 2 * kStep, a0, b0);
-        settle(k0 + kStep, a1, b1);
-        if (k0 + kStep < w_in) mma(a1, b1);
-    }
-    return acc;
-}
 
 __global__ __launch_bounds__(kMlpThreads) void k_grouped_mlp_max(const MlpArgs A) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -743,6 +680,11 @@ dim3 grid_rows(int64_t per_row, int64_t rows) {
 }
 
 }  // namespace
+
+namespace ssf_pn2_detail {
+int32_t fail(int32_t code, const char* msg) { return ::fail(code, msg); }
+int32_t hip_status(hipError_t e, const char* what) { return ::hip_status(e, what); }
+}  // namespace ssf_pn2_detail
 
 // ------------------------------------------------------------------------------------------
 extern "C" {

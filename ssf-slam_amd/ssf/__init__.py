@@ -10,6 +10,9 @@ from .pose import mask_and_pose, slove_RT_by_SVD  # noqa: F401
 from . import loop  # noqa: F401  (mapOptmization loop closure: voxel grid, ICP, LoopCloser)
 from .map_cloud import MapCloud  # noqa: F401  (mapOptmization's accumulated map cloud)
 from . import pointnet2  # noqa: F401  (TFlow point-set operators: pointutils surface)
+from . import tflow  # noqa: F401  (the TFlow network: cost volume, warping, flow regressor)
+from .tflow import CostVolume, PointWarping, RefineFlowRegressor, TFlow  # noqa: F401
 
 __all__ = ["Frontend", "PlaneBatch", "frame_offsets", "identity_poses", "register_plan", "SSFError",
            "mask_and_pose", "slove_RT_by_SVD", "loop", "MapCloud", "pointnet2"]
+__all__ += ["tflow", "CostVolume", "PointWarping", "RefineFlowRegressor", "TFlow"]

@@ -46,10 +46,12 @@ EXPORTS = [
 PN2_EXPORTS = [
     "ssf_pn2_last_error", "ssf_pn2_furthest_point_sample", "ssf_pn2_knn", "ssf_pn2_three_nn",
     "ssf_pn2_gather", "ssf_pn2_three_interpolate", "ssf_pn2_upsample_flow",
-    "ssf_pn2_group_relative", "ssf_pn2_grouped_mlp_max",
+    "ssf_pn2_group_relative", "ssf_pn2_grouped_mlp_max", "ssf_pn2_grouped_mlp",
+    "ssf_pn2_pair_attention", "ssf_pn2_segment_softmax_sum",
 ]
 PN2_KNN_MAX, PN2_UPSAMPLE_MAX_SPARSE = 32, 4096
 PN2_MLP_MAX_LAYERS, PN2_MLP_MAX_WIDTH = 3, 512
+PN2_GMLP_MAX_IN, PN2_ATTN_MAX_C = 766, 512
 
 ICP_OUT_STRIDE = 24
 ICP_OUT = dict(T=0, FITNESS=16, CONVERGED=17, ITERATIONS=18, STATE=19, NCORR=20)
@@ -205,6 +207,10 @@ def lib():
     L.ssf_pn2_group_relative.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.ssf_pn2_grouped_mlp_max.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp,
                                           vp, vp]
+    L.ssf_pn2_grouped_mlp.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32,
+                                      vp, vp, vp, vp, vp, i32, vp, vp]
+    L.ssf_pn2_pair_attention.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.ssf_pn2_segment_softmax_sum.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     for name in PN2_EXPORTS[1:]:
         getattr(L, name).restype = i32
     _lib = L
