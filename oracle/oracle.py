@@ -9,7 +9,9 @@ Parity status: the Python half (GMM mask, Kabsch, quaternion) is pinned against 
 vectors generated from the reference's own scripts/PointCloudOdometry_noSeg.py; the C++ half
 (frameFeature.cpp / lidarOdometry_onlyPC.cpp) is PARITY UNPINNED against the reference
 binary (ROS/PCL/Eigen/Ceres are absent, so it cannot be built) and is pinned only by
-known-answer tests.  See oracle/ssf_oracle.h and DESIGN.md.
+known-answer tests.  The 3x3 algebra both halves end in (svd3, kabsch, quat_from_R, the Umeyama
+and convergence block of icp) is pinned to an independent numpy yardstick
+(tests/rigid_reference.py, tests/test_rigid_host.py).  See oracle/ssf_oracle.h and DESIGN.md.
 """
 from __future__ import annotations
 

@@ -1183,6 +1183,24 @@ void orc_svd3(const double A[9], double U[9], double S[3], double Vt[9]) {
             Vt[k * 3 + i] = v[i][j];
         }
     }
+    /* Rank 0 / rank 1: complete U to a right-handed orthonormal basis (the block below then sets
+     * u2 = u0 x u1).  An exactly zero singular value left a zero column above; an exactly rank-1
+     * input can also leave a ~1e-157 column PARALLEL to u0 (equal-magnitude components round alike,
+     * the residual shrinks by 1e-16 a sweep until the |gamma| <= 1e-300 skip), so the test is the
+     * relative one of the block below, never reached by a full-rank or rank-2 input. */
+    if (S[0] == 0.0) {                   /* zero matrix: U = I, as LAPACK returns */
+        u[0][0] = 1.0; u[1][1] = 1.0;
+    } else if (!(S[1] > 1e-12 * S[0])) { /* rank 1: u1 = u0 x e / |u0 x e|, e the axis u0 leans on least */
+        const double ax = fabs(u[0][0]), ay = fabs(u[1][0]), az = fabs(u[2][0]);
+        const double ex = (ax <= ay && ax <= az) ? 1.0 : 0.0;
+        const double ey = (ex == 0.0 && ay <= az) ? 1.0 : 0.0;
+        const double ez = 1.0 - ex - ey;
+        const double wx = u[1][0] * ez - u[2][0] * ey;
+        const double wy = u[2][0] * ex - u[0][0] * ez;
+        const double wz = u[0][0] * ey - u[1][0] * ex;
+        const double wn = sqrt(wx * wx + wy * wy + wz * wz);
+        u[0][1] = wx / wn; u[1][1] = wy / wn; u[2][1] = wz / wn;
+    }
     if (!(S[2] > 1e-12 * S[0])) { /* rank-deficient H (coplanar points): right-handed u3, v3 */
         u[0][2] = u[1][0] * u[2][1] - u[2][0] * u[1][1];
         u[1][2] = u[2][0] * u[0][1] - u[0][0] * u[2][1];

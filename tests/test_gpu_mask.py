@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from helpers import frame
+from rigid_reference import quat_xyzw, rot_from_quat
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
@@ -317,6 +318,11 @@ def test_kabsch_golden(dev):
         assert _rot_angle(R, g[f"R{c}"]) < 1e-6, c
         assert np.abs(o[0:3] - g[f"t{c}"]).max() < 1e-5, c
         assert np.abs(R - g[f"R{c}"]).max() < 1e-9, c          # observed ~1e-15
+        # q: pyquaternion's trace method on the reference's own R (tests/rigid_reference.py), 2e-9
+        # (each component is at most two entries of R times a factor <= 0.5, plus the scale term)
+        qr, branch, _ = quat_xyzw(g[f"R{c}"])
+        assert np.abs(o[3:7] - qr).max() < 2e-9, c
+        assert o[3 + "xyzw".index(branch)] > 0 and np.abs(rot_from_quat(o[3:7]) - R).max() < 1e-9, c
 
 
 def test_kabsch_golden_f32_inputs(dev):
@@ -332,6 +338,12 @@ def test_kabsch_golden_f32_inputs(dev):
         assert out[0, 16] == 0
         assert np.abs(out[0, 7:16].reshape(3, 3) - g[f"R{c}"]).max() < 1e-5
         assert np.abs(out[0, 0:3] - g[f"t{c}"]).max() < 1e-4
+        # q against the trace method on the reference's R: twice the R bar, as 2e-9 is to 1e-9 on
+        # the f64 path; and q is the quaternion of the R this frame returned, to the f64 bar
+        qr, branch, _ = quat_xyzw(g[f"R{c}"])
+        assert np.abs(out[0, 3:7] - qr).max() < 2e-5, c
+        assert out[0, 3 + "xyzw".index(branch)] > 0
+        assert np.abs(rot_from_quat(out[0, 3:7]) - out[0, 7:16].reshape(3, 3)).max() < 1e-9, c
 
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "gmm_noseg_case*.npz"))))
