@@ -168,7 +168,9 @@ int32_t ssf_plane_table_batch(ssf_ctx* ctx, void* stream, int32_t n_frames,
  *   max_plane_points     host upper bound of plane points in any frame (grid sizing)
  *   d_pose_rel [P*7] in: warm start q_last_curr/t_last_curr (the previous pair's solution,
  *                    :164,251-252); out: the solution.  Last frames with <= 10 points leave
- *                    it unchanged (:158).
+ *                    it unchanged (:158).  PRECONDITION: q is a unit quaternion (the solve's
+ *                    Jacobian is the parameterisation's for |q| = 1; a chain's drift of 1e-12
+ *                    is inside the bars, |q| = 1 +- 1e-3 moves a step by ~1e-8 rad).
  *   d_pose_abs [P*7] nullable; in: q_0_last,t_0_last; out: q_0_curr,t_0_curr (:87-90).
  *   d_log      nullable [P*max_iter*10] doubles per iteration: q(4) t(3) cost status radius
  *   d_nlog     nullable [P] iterations logged;  d_ncorr nullable [P] correspondences used

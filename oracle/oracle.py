@@ -102,6 +102,9 @@ def lib():
     L.orc_solve.argtypes = [f32p, f32p, f32p, C.c_int64, C.c_int32, C.c_int32, f64p, f64p, f64p,
                             f64p, f64p, C.POINTER(C.c_int32)]
     L.orc_solve.restype = C.c_int32
+    L.orc_solve2.argtypes = [f32p, f32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
+                             C.c_int32, f64p, f64p, f64p, f64p, f64p, C.POINTER(C.c_int32)]
+    L.orc_solve2.restype = C.c_int32
     L.orc_register_pair.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.c_float, C.c_int32,
                                     C.c_int32, f64p, f64p, f64p, f64p, f64p, C.POINTER(C.c_int32)]
     L.orc_register_pair.restype = C.c_int64
@@ -296,6 +299,22 @@ def solve(po, pa, nrm, mode=MODE_CERES_LM, max_iter=8, q_init=(0, 0, 0, 1), t_in
                     nr if c else np.zeros(3, np.float32), c, mode, max_iter,
                     np.asarray(q_init, np.float64), np.asarray(t_init, np.float64), q, t, log,
                     C.byref(nl))
+    return q, t, log[:LOG_STRIDE * nl.value].reshape(-1, LOG_STRIDE)
+
+
+def solve2(po, pa, nrm, epo, ec, eu, mode=MODE_CERES_LM, max_iter=8, q_init=(0, 0, 0, 1),
+           t_init=(0, 0, 0)):
+    """orc_solve2: plane blocks (po, pa, nrm) plus point-to-line blocks (epo, centroid, direction)"""
+    def flat(a):
+        a = np.ascontiguousarray(a, np.float32).reshape(-1)
+        return (a if a.size else np.zeros(3, np.float32)), a.size // 3
+    (po, c), (pa, _), (nr, _) = flat(po), flat(pa), flat(nrm)
+    (epo, ce), (ec, _), (eu, _) = flat(epo), flat(ec), flat(eu)
+    q = np.zeros(4); t = np.zeros(3)
+    log = np.zeros(LOG_STRIDE * (max_iter + 2))
+    nl = C.c_int32(0)
+    lib().orc_solve2(po, pa, nr, c, epo, ec, eu, ce, mode, max_iter, np.asarray(q_init, np.float64),
+                     np.asarray(t_init, np.float64), q, t, log, C.byref(nl))
     return q, t, log[:LOG_STRIDE * nl.value].reshape(-1, LOG_STRIDE)
 
 

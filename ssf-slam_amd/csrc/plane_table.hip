@@ -133,26 +133,33 @@ SSF_DEV int bounded_decides(const float4* __restrict__ P, int m, const double (&
     return nq >= 2 ? 1 : 0;
 }
 
-// A deferred query (6 <= K1 < 30 keys inside 1 m, fewer than two other-ring points among ranks
-// 5..K1-1) has a valid plane only if NO point of ranks K1..29 lies on another ring (0..63):
-// the pick (lidarOdometry_onlyPC.cpp:180-198) takes the first such point, n becomes its rank and
-// dis2[n] >= 1 fails :207.  If none is there, n is a rank inside 1 m and the plane uses only
-// points inside 1 m.  kk is exact for every key closer than lim.  Returns 1 when the list
-// is complete (table_finish decides), 2 when an other-ring point among the exact ranks >= K1
-// decides it invalid, 0 when the ranks beyond lim are still needed.
+// A deferred query has 6 <= K1 < 30 keys inside 1 m.  bounded_decides defers it because fewer
+// than two other-ring points (rings 0..63) lie among ranks 5..K1-1 -- or, in a frame of at most
+// kK points, whatever it holds.  nq counts those points (the keys are in rank order, so every key
+// inside 1 m comes before the first beyond it):
+//   nq >= 2  the pick (lidarOdometry_onlyPC.cpp:180-198) stops at the second of them, inside
+//            1 m; no point beyond 1 m can invalidate it and the plane uses only exact ranks;
+//   nq < 2   the plane is valid only if NO point of ranks K1..29 lies on another ring: the pick
+//            takes the first such point, n becomes its rank and dis2[n] >= 1 fails :207.  If none
+//            is there, n is a rank inside 1 m and the plane uses only points inside 1 m.
+// kk is exact for every key closer than lim.  Returns 1 when the list is complete or nq >= 2
+// (table_finish decides), 2 when an other-ring point among the exact ranks >= K1 decides it
+// invalid, 0 when the ranks beyond lim are still needed.
 SSF_DEV int deferred_decides(const float4* __restrict__ P, const double (&kk)[kK], float lim) {
     if (key_dist(kk[kK - 1]) < lim) return 1;
     const int prow = row_of(P[key_index(kk[0])].w);
-    int dec = 0;
+    int dec = 0, nq = 0;
 #pragma unroll
     for (int k = 5; k < kK; ++k) {
         const float d = key_dist(kk[k]);
-        if (d >= 1.0f && d < lim) {
+        if (d < lim) {
             const int row = row_of(P[key_index(kk[k])].w);
-            if (row != prow && row >= 0 && row <= 63) dec = 2;
+            const bool other = row != prow && row >= 0 && row <= 63;
+            if (d < 1.0f) nq += other;
+            else if (other && nq < 2) dec = 2;
         }
     }
-    return dec;
+    return nq >= 2 ? 1 : dec;
 }
 
 SSF_DEV void table_finish(const float4* __restrict__ P, int m, float plane_max, int64_t o,

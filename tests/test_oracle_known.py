@@ -72,6 +72,24 @@ def test_plane_fit_exact_plane(oracle):
     assert np.abs(np.abs(nrm[:, 2]) - 1).max() < 1e-6
     # gated rank: the 6th neighbour (n = 5) unless different-row points were collected
     assert set(np.unique(gate)) <= set(range(5, 30))
+    # and against the independent yardstick: the same five points and gated rank for every point
+    # whose rank order no near tie decides, the same validity, the normal within the float32 fit's
+    # error FIT_C kappa(A) 2^-24 (tests/test_registration_host.py)
+    import registration_reference as ref
+    from registration_cases import FIT_C
+    compared = 0
+    for a in range(m):
+        pk = ref.plane_pick(P, a)
+        if min(pk["gap45"], pk["gap_n"]) < 1e-5 or pk["gate_gap"] < 1e-5:
+            continue
+        assert np.array_equal(pick[a], pk["pick"]) and gate[a] == pk["n"], a
+        fit = ref.plane_fit5(P[pk["pick"], :3], 0.05)
+        assert fit["valid"] and fit["rank"] == 3, a
+        n64 = nrm[a].astype(np.float64)
+        ang = np.arctan2(np.linalg.norm(np.cross(n64, fit["normal"])), n64 @ fit["normal"])
+        assert ang <= FIT_C * fit["kappa"] * 2.0 ** -24, (a, ang, fit["kappa"])
+        compared += 1
+    assert compared > 0.9 * m
 
 
 def test_quaternion_plus_and_accumulate(oracle):
@@ -102,6 +120,16 @@ def test_lm_recovers_known_transform(oracle):
                                  mode=mode, max_iter=iters)
         assert np.abs(t - tt).max() < 1e-4, (mode, t)
         assert abs(abs(np.dot(q, qt)) - 1) < 1e-8
+        # and against the independent yardstick (jets, lstsq on the Jacobian), step by step: the
+        # statuses through its last clear decision, every pose within a tenth of the project's bars
+        import registration_reference as ref
+        p32, a32, n32 = po.astype(np.float32), pa.astype(np.float32), nrm.astype(np.float32)
+        sol = (ref.solve_gn if mode else ref.solve_lm)(p32, a32, n32, [0, 0, 0, 1], [0, 0, 0], iters)
+        rows = len(sol["log"]) if mode else ref.clear_rows(sol["margins"])
+        assert rows >= 2 and np.array_equal(log[:rows, 8], sol["log"][:rows, 8]), (mode, log[:, 8], sol["log"][:, 8])
+        for k in range(rows):
+            assert np.abs(log[k, 4:7] - sol["log"][k, 4:7]).max() < 1e-6, (mode, k)
+            assert ref.quat_angle(log[k, :4], sol["log"][k, :4]) < 1e-7, (mode, k)
 
 
 def test_oracle_register_on_synthetic_pair(oracle):
