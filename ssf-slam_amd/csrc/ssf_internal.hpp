@@ -45,9 +45,9 @@ constexpr int kMaxRows = 64;
 #define SSF_MASK_MAX_SPLIT 32
 #endif
 constexpr int kMaskMaxSplit = SSF_MASK_MAX_SPLIT;   // work-groups per frame of the GMM fit at most
-// candidate flag bytes of a batch (k_bin_curv -> k_select, one per ring position, per frame
-// 64-byte aligned) and the curvature fix-up lists (per-frame counts, then ring positions at the
-// frame offsets)
+// scratch of the binned feature stage (feat_bin.hip): the candidate flag bytes of a batch
+// (k_bin_curv -> k_select, one per ring position, per frame 64-byte aligned) and the curvature
+// fix-up lists (per-frame counts, then ring positions at the frame offsets)
 size_t flag_bytes(int64_t total, int n_frames);
 size_t fix_bytes(int64_t total, int n_frames);
 
@@ -58,7 +58,7 @@ struct alignas(16) CorrRec {
     float n[3];  float pad1;    // plane normal (float, as matX0)
 };
 
-// ---- launchers (features.hip) ----
+// ---- the feature stage: its arguments, scratch sizes and launcher (features.hip) ----
 // Edge selection of launch_extract_planes (beyond the reference; nullptr = planes only):
 // the per-row selection slots in ctx scratch, the compacted edge cloud (float4 x, y, z,
 // intensity at the frame offsets) and per-frame counts out (the candidates ride in bit 1 of
@@ -70,16 +70,17 @@ struct EdgeSel {
     float4* out;
     int32_t* count;
 };
-// Scratch of the single-read feature stage (k_feat_chunk / k_feat_select, frames of at most
-// 128 chunks): per-(chunk, row) counts -> row bases, u16 chunk positions per own-tile slot, the
-// chunks' candidate / unresolved bit planes, and (debug outputs only) chunk-major curvature.
+// Scratch of the single-read feature stage (feat_wave.hip, feat_chunk.hip, feat_select.hip;
+// frames of at most 128 chunks): per-(chunk, row) counts -> row bases, u16 chunk positions per
+// own-tile slot, the chunks' candidate / unresolved / edge bit planes, (debug outputs only)
+// chunk-major curvature, and which kernel did each (frame, chunk) block.
 struct FeatScratch {
     const void* rtab;   // the ring-id table (build_ring_table), device copy
     int32_t* cnt;       // feat_cnt_bytes
     uint16_t* gidx;     // feat_idx_bytes
     uint64_t* gbits;    // feat_bits_bytes
     float* curv_cm;     // total floats (debug), else nullptr
-    uint8_t* irr;       // feat_irr_bytes: per (frame, chunk) block, 1 = not a regular window
+    uint8_t* irr;       // feat_irr_bytes: per (frame, chunk) block, the kernel that did it (kIrr*)
     uint8_t* lmap;      // feat_lmap_bytes: per regular block, row -> lane (64 B)
 };
 size_t feat_idx_bytes(int64_t total, int n_frames);
@@ -88,12 +89,8 @@ size_t feat_cnt_bytes(int n_frames, int64_t max_pts);
 size_t feat_irr_bytes(int n_frames, int64_t max_pts);
 size_t feat_lmap_bytes(int n_frames, int64_t max_pts);
 bool feat_single_read(int64_t max_pts);
-// host: the ring-id table of n_rows (16 / 64) and ring_chain (SSF_RING_CHAIN_*) into out
-// (ring_table_bytes); 0 or a negative code
-int build_ring_table(int n_rows, int chain, void* out_host);
-size_t ring_table_bytes();
-// Scratch that only the binning stage reads (k_bin_count / k_bin_scan / k_bin_curv / k_select,
-// frames beyond the single-read capacity).
+// Scratch that only the binned stage reads (feat_bin.hip: k_bin_count / k_bin_scan / k_bin_curv /
+// k_select, frames beyond the single-read capacity).
 struct BinScratch {
     int8_t* rid;        // ring id per input point (total bytes)
     int32_t* hist;      // per (frame, chunk, row) counts
@@ -123,6 +120,37 @@ struct FeatOut {
 hipError_t launch_extract_planes(hipStream_t s, const ssf_config& cfg, int n_frames,
                                  const FeatFrames& in, const FeatOut& out, int32_t* sel,
                                  const BinScratch& bin, const FeatScratch& fs, const EdgeSel* edge);
+// launch_extract_planes' stages, each beside its kernels; launch_extract_planes checks for
+// errors.  What they share: the launch's arguments, n_chunks (the chunks of the largest frame),
+// dbg (the debug outputs are asked for: the <kDebug> instantiations) and the edge selection --
+// es holds the values the kernels are passed when it is off (edge = false).
+struct FeatLaunch {
+    hipStream_t s;
+    const ssf_config& cfg;
+    int n_frames, n_chunks;
+    const FeatFrames& in;
+    const FeatOut& out;
+    int32_t* sel;
+    bool dbg, edge;
+    EdgeSel es;
+};
+// ---- ring_table.hip ----
+// host: the ring-id table of n_rows (16 / 64) and ring_chain (SSF_RING_CHAIN_*) into out
+// (ring_table_bytes); 0 or a negative code
+int build_ring_table(int n_rows, int chain, void* out_host);
+size_t ring_table_bytes();
+// ---- launchers (feat_wave.hip, feat_chunk.hip, feat_select.hip): the single-read stage ----
+// fs: the scratch this launch uses (curv_cm, irr, lmap null when it does not).  all: no
+// k_feat_wave_reg ran, k_feat_wave_run takes every chunk.  launch_feat_chunk does the blocks
+// flagged kIrrGeneral (fs.irr) or every block (no fs.irr).
+void launch_feat_wave_reg(const FeatLaunch& a, const FeatScratch& fs);
+void launch_feat_wave_run(const FeatLaunch& a, const FeatScratch& fs, bool all);
+void launch_feat_chunk(const FeatLaunch& a, const FeatScratch& fs);
+void launch_feat_select(const FeatLaunch& a, const FeatScratch& fs);
+void launch_feat_debug(const FeatLaunch& a, const FeatScratch& fs);
+// ---- launcher (feat_bin.hip): the binned stage; rtab: the ring-id table (required) ----
+size_t fix_head(int n_frames);   // bytes of the fix-up lists' per-frame counts (fix_bytes)
+hipError_t launch_feat_bin(const FeatLaunch& a, const BinScratch& bin, const void* rtab);
 
 // ---- launchers (plane_table.hip) ----
 hipError_t launch_plane_table(hipStream_t s, const ssf_config& cfg, int n_frames,

@@ -89,7 +89,9 @@ def _single_batch(xyzi: torch.Tensor, device) -> PlaneBatch:
 
 
 class FrameFeatureNode:
-    """src/frameFeature.cpp cloudHandler on the device (k_bin_count / k_bin_scan / k_bin_curv / k_select)."""
+    """src/frameFeature.cpp cloudHandler on the device: the single-read stage (k_feat_wave_reg /
+    k_feat_wave_run / k_feat_chunk_flagged, then k_feat_select); frames above 262144 points take
+    the binned stage (k_bin_count / k_bin_scan / k_bin_curv / k_select)."""
 
     def __init__(self, publish, n_rows: int = 64, device=None, frontend: Frontend | None = None):
         self.fe = frontend or Frontend(n_rows, device=device)

@@ -31,8 +31,10 @@ def _pair(b, a, c):
     return last, curr
 
 
-@pytest.mark.parametrize("rows,n_az", [(64, 1875), (16, 1800), (16, 4500)])
+@pytest.mark.parametrize("rows,n_az", [(64, 1875), (16, 1800), (16, 4500), (64, 4100)])
 def test_edge_features_bitexact(oracle, dev, rows, n_az):
+    """(64, 4100): 262 400 points, just above the single-read capacity -- the binned stage's edge
+    instantiations (k_bin_curv, k_select)"""
     import ssf
     fe = ssf.Frontend(rows, device=dev.index)
     fe.edge_config()
@@ -62,6 +64,25 @@ def test_edge_config_and_masked(oracle, dev):
     P, E = oracle.extract_features(c[keep != 0], 64, edge_min=0.2, edge_span=5)
     assert np.array_equal(pb.frame(0).cpu().numpy(), P)
     assert np.array_equal(eb.frame(0).cpu().numpy(), E)
+
+
+def test_edge_features_of_wide_points(oracle, dev):
+    """Points more than 4096 floats apart: no wave kernel runs, the edge instantiation of
+    k_feat_chunk (not k_feat_chunk_flagged) does every chunk.  64 x 70 points at stride 4097
+    (three chunks); plane and edge lists bit-exact vs the oracle."""
+    import ssf
+    fe = ssf.Frontend(64, device=dev.index)
+    fe.edge_config()
+    c = frame(10, 1, n_az=70)[0]
+    wide = np.full((len(c), 4097), 7.0, np.float32)
+    wide[:, :3] = c
+    off, h_off = ssf.frame_offsets([len(c)], dev)
+    pb, eb = fe.extract_features_batch(torch.from_numpy(wide).to(dev), off, h_off)
+    torch.cuda.synchronize()
+    P, E = oracle.extract_features(c, 64)
+    assert np.array_equal(pb.frame(0).cpu().numpy().view(np.uint32), P.view(np.uint32))
+    g = eb.frame(0).cpu().numpy()
+    assert len(E) > 50 and np.array_equal(g.view(np.uint32), E.view(np.uint32)), (len(g), len(E))
 
 
 def test_edge_table_bitexact(oracle, dev):

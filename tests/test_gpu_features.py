@@ -233,7 +233,7 @@ def test_masked_rows_with_0_1_2_points(oracle, dev):
 
 
 def _planes_product(fe, clouds, dev):
-    """the product path (no debug outputs: k_bin_curv<false> / k_curv_fixup<false>)"""
+    """the product path (no debug outputs: the <kDebug = false> instantiations of every kernel)"""
     import ssf
     t = torch.from_numpy(np.ascontiguousarray(np.concatenate(clouds))).to(dev)
     off, h_off = ssf.frame_offsets([c.shape[0] for c in clouds], dev)
@@ -242,8 +242,10 @@ def _planes_product(fe, clouds, dev):
 
 
 def test_curvature_halo_and_fixup_orders(oracle, dev):
-    """k_bin_curv reads a stencil from its window (the chunk +- 384 input points) when the row
-    has 5 points on each side there, and leaves the rest to k_curv_fixup (taps through the ring
+    """A chunk kernel (k_feat_wave_reg / k_feat_wave_run / k_feat_chunk; k_bin_curv for larger
+    frames) reads a stencil from its window (the chunk +- 384 input points) when the row has 5
+    points on each side there, and leaves the rest to the frame kernel (k_feat_select: unresolved
+    points, taps through the chunk-major index; k_select: the fix-up list, taps through the ring
     index).  Input orders that exercise every case: azimuth order with whole azimuth columns
     missing in some rows (sparse rows: a few stencils open), row-major order (a chunk is one or
     two rows: every stencil in the window), a fully shuffled frame (almost every stencil open),
@@ -285,7 +287,7 @@ def test_product_path_equals_debug_path(oracle, dev):
 @pytest.mark.parametrize("chain", ["float", "double"])
 @pytest.mark.parametrize("n_rows", [64, 16])
 def test_ring_id_table_edges(oracle, dev, n_rows, chain):
-    """The single-read stage's ring id (one table cell + one compare, features.hip
+    """The single-read stage's ring id (one table cell + one compare, feat_common.hpp
     ring_id_table) on the exact ratios where the reference's row id changes, +-3 ulps around each
     (points (1, 0, ratio): z / sqrt(1) is the ratio itself in both chains), every cell edge, the
     origin (0/0) and +-inf ratios: the ring-ordered cloud equals the oracle's under the same
@@ -315,7 +317,7 @@ def test_ring_id_table_edges(oracle, dev, n_rows, chain):
 def test_frames_above_single_read_capacity(oracle, dev):
     """k_feat_select holds a frame's chunk counts for at most kFeatMaxChunks = 128 chunks
     (262 144 points); a launch whose frames may be larger takes the round-3 kernels
-    (k_bin_count / k_bin_scan / k_bin_curv / k_select, features.hip launch_extract_planes).  A
+    (k_bin_count / k_bin_scan / k_bin_curv / k_select, feat_bin.hip launch_feat_bin).  A
     64 x 4200 = 268 800-point frame, the same frame shuffled, and a short one in the same launch:
     ring cloud, curvature bits and plane lists bit-exact, debug and product instantiations."""
     import ssf
@@ -329,6 +331,24 @@ def test_frames_above_single_read_capacity(oracle, dev):
     got = _planes_product(fe, clouds, dev)
     for f, cl in enumerate(clouds):
         assert np.array_equal(got[f].view(np.uint32), oracle.extract_planes(cl, 64).view(np.uint32)), f
+
+
+def test_point_stride_beyond_the_wave_kernels(oracle, dev):
+    """k_feat_wave_reg and k_feat_wave_run address a window with 32-bit offsets, so a launch whose
+    points are more than 4096 floats apart runs neither: k_feat_chunk (not k_feat_chunk_flagged)
+    does every chunk.  64 x 70 points at stride 4097: three chunks, the middle one with a full
+    halo on both sides.  Ring cloud, curvature bits and plane list bit-exact vs the oracle, debug
+    and product instantiations."""
+    import ssf
+    c = frame(10, 1, n_az=70)[0]
+    fe = ssf.Frontend(64, device=dev.index or 0)
+    out, h_off = _run(fe, [c], dev, stride=4097)
+    _check_frame(oracle, fe, out, h_off, 0, c, 64)
+    pad = np.full((len(c), 4097), 7.0, np.float32)
+    pad[:, :3] = c
+    off, h_off = ssf.frame_offsets([len(c)], dev)
+    got = fe.extract_planes_batch(torch.from_numpy(pad).to(dev), off, h_off).frame(0).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), oracle.extract_planes(c, 64).view(np.uint32))
 
 
 def test_regular_windows_mixed_with_flagged_blocks(oracle, dev):
@@ -412,7 +432,7 @@ def test_carla_layout_frames(oracle, dev):
 
 
 def test_run_kernel_orders_gaps_and_fallbacks(oracle, dev):
-    """k_feat_wave_run's cases (features.hip): rows in DESCENDING order (own-tile slots are not the
+    """k_feat_wave_run's cases (feat_wave.hip): rows in DESCENDING order (own-tile slots are not the
     input order: the bit planes move run by run), points in no row between runs (gaps) and inside
     a run (the row then forms two runs in a chunk: left to k_feat_chunk), rows alternating in
     100-point blocks (a row in several runs per chunk: fallback), many short runs (> 64 runs in a

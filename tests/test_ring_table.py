@@ -1,5 +1,5 @@
-"""The ring-id table of the feature stage (features.hip build_ring_table / ring_id_table): for every
-ratio, one cell lookup + one compare must give the reference's row id (frameFeature.cpp:57-73 as
+"""The ring-id table of the feature stage (ring_table.hip build_ring_table, feat_common.hpp
+ring_id_table): for every ratio, one cell lookup + one compare must give the reference's row id (frameFeature.cpp:57-73 as
 oracle/ssf_oracle.c orc_ring_angle computes it under either overload resolution):
   float chain (default): ratio z / sqrtf(r2), atanf, `* 180` in float, `/ M_PI` in double;
   double chain: ratio (double)z / sqrt((double)r2), atan and the scaling in double.
