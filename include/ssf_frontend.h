@@ -516,7 +516,14 @@ int32_t ssf_icp_batch(ssf_ctx* ctx, void* stream, int32_t n_prob, const float* d
  * standard deviations.  Stops when |cost_{k-1} - cost_k| <= func_tol * cost_{k-1} (func_tol 0:
  * exactly max_iter steps); steps are never rejected.  Edges with |i - j| == 1 and the prior form
  * the block-tridiagonal part; every other edge is a loop edge, at most SSF_PGO_MAX_LOOPS per
- * graph.  A graph that ends with SSF_PGO_EMPTY, _BAD_INPUT, _TOO_MANY_LOOPS or _NOT_PD keeps its
+ * graph.  The host picks a graph's kernel from its counts: up to 32 edges beyond the K - 1 of a
+ * chain and it is solved with a lane per right-hand side; more, and the loop edges go through in
+ * passes, with a capacitance matrix of (6 min(E - (K - 1), SSF_PGO_MAX_LOOPS))^2 doubles in the
+ * context scratch (18.9 MB at the cap).  One call may mix both kinds; a graph's result does not
+ * depend on the rest of the batch.  A graph with more loop edges than it has edges beyond
+ * K - 1 lacks a chain link and ends with SSF_PGO_NOT_PD; more than SSF_PGO_MAX_LOOPS loop edges
+ * end with SSF_PGO_TOO_MANY_LOOPS and the count in SSF_PGO_OUT_LOOPS.  A graph that ends with
+ * SSF_PGO_EMPTY, _BAD_INPUT, _TOO_MANY_LOOPS or _NOT_PD keeps its
  * poses bit for bit and does not affect the other graphs.  Asynchronous on stream.  SSF_E_ARG
  * (before any HIP call) on a null context or pointer, a negative count, max_iter outside
  * [0, SSF_PGO_MAX_ITER] or host offsets that do not start at 0 or decrease. */
@@ -524,7 +531,7 @@ typedef struct {
     int32_t max_iter;       /* 8: the isam->update calls of a loop closure (:281-288)  */
     double func_tol;        /* 1e-6: the front-end's Ceres function tolerance          */
 } ssf_pgo_params;
-#define SSF_PGO_MAX_LOOPS 32
+#define SSF_PGO_MAX_LOOPS 256
 #define SSF_PGO_MAX_ITER 1024
 #define SSF_PGO_OUT_STRIDE 8
 enum {

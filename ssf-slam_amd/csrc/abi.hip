@@ -1070,14 +1070,16 @@ int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double*
             return fail(c, SSF_E_ARG, "pose_graph_batch: offsets not monotone");
     c->pgo_h.resize((size_t)n_graphs);
     size_t total = 0;
+    bool any_narrow = false, any_wide = false;
     for (int g = 0; g < n_graphs; ++g) {
         ssf::PgoGraph& G = c->pgo_h[(size_t)g];
         G.node0 = h_node_off[g]; G.K = h_node_off[g + 1] - h_node_off[g];
         G.edge0 = h_edge_off[g]; G.E = h_edge_off[g + 1] - h_edge_off[g];
         G.lcap = std::min(std::max(G.E - (G.K - 1), 0), SSF_PGO_MAX_LOOPS);
-        G.pad = 0;
+        G.wide = ssf::pgo_graph_wide(G.K, G.E);
+        (G.wide ? any_wide : any_narrow) = true;
         G.scratch_off = (int64_t)total;
-        total += ssf::pgo_graph_doubles(G.K, G.E, G.lcap);
+        total += ssf::pgo_graph_doubles(G.K, G.E, G.lcap, G.wide != 0);
     }
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(c, stream);
@@ -1086,7 +1088,7 @@ int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double*
     SSF_TRY_HIP(c, c->pgo_scratch.ensure(sizeof(double) * total), "alloc pose-graph scratch");
     SSF_TRY_HIP(c, hipMemcpyAsync(c->pgo_desc.p, c->pgo_h.data(), sizeof(ssf::PgoGraph) * (size_t)n_graphs,
                                   hipMemcpyHostToDevice, s), "H2D pose-graph descriptors");
-    hipError_t e = ssf::launch_pose_graph(s, n_graphs, c->pgo_desc.as<ssf::PgoGraph>(), d_pose, d_node_off,
+    hipError_t e = ssf::launch_pose_graph(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose, d_node_off,
                                           d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
                                           d_prior_var, prm->max_iter, prm->func_tol,
                                           c->pgo_scratch.as<double>(), d_stats, d_cost_log);

@@ -22,6 +22,16 @@
 //     Woodbury   capacitance C = I + A T^-1 A^T (6L x 6L), dense Cholesky with one thread per
 //                row, dx = T^-1 b - T^-1 A^T C^-1 A T^-1 b
 //     retract    one thread per node
+//   The above is k_pose_graph, for graphs with at most 32 edges beyond the K - 1 of a chain
+//   (so at most 32 loop edges).  Every other graph is k_pose_graph_wide's (up to
+//   SSF_PGO_MAX_LOOPS loop edges); same phases, except
+//     substitute the 6 L + 1 columns go through kPgoThreads at a time in a 6K x kPgoThreads pass
+//                buffer; a lane folds its solved column into C (column 0 into u = A T^-1 (-g))
+//                before the buffer is reused, so T^-1 A^T is never held whole
+//     Woodbury   the loop list, C (order up to 1536) and its vectors live in the graph's scratch;
+//                dense Cholesky with the rows strided over the threads, by panels of columns;
+//                dx = T^-1 (-g - A^T w): one more single-column substitution on lane 0
+//   The host picks the kernel (PgoGraph::wide, from K and E); the two share pgo_solve.
 //   No inter-work-group communication of any kind.  A graph writes its poses back only when it
 //   ends with SSF_PGO_OK / SSF_PGO_CONVERGED: it iterates on a copy in the context scratch.
 //   Every loop bound is a count the prologue validated (K, E from the host descriptor checked
@@ -35,13 +45,22 @@ namespace ssf {
 
 constexpr int kPgoThreads = 256;
 constexpr int kPgoRec = 78;                       // r[6], Ji[36], Jj[36] (row-major, whitened)
-constexpr int kPgoMaxN = 6 * SSF_PGO_MAX_LOOPS;   // capacitance order
+constexpr int kPgoNarrowLoops = 32;               // up to here: one lane per right-hand side
+constexpr int kPgoMaxN = 6 * kPgoNarrowLoops;     // capacitance order of the narrow path
 constexpr int kPgoTile = 2048;                    // edge index pairs staged in LDS (16 KiB)
+constexpr int kPgoWideRows = (6 * SSF_PGO_MAX_LOOPS + kPgoThreads - 1) / kPgoThreads;   // per thread
+constexpr int kPgoPanel = 8;                      // columns a sweep of the wide Cholesky updates
 static_assert(kPgoMaxN + 1 <= kPgoThreads, "one lane per right-hand side");
+static_assert(kPgoNarrowLoops <= SSF_PGO_MAX_LOOPS, "the narrow path is a subset");
 
-size_t pgo_graph_doubles(int K, int E, int lcap) {
+bool pgo_graph_wide(int K, int E) { return E - (K - 1) > kPgoNarrowLoops; }
+
+size_t pgo_graph_doubles(int K, int E, int lcap, bool wide) {
     const size_t k = (size_t)K, nc = 6 * (size_t)lcap + 1, n = 6 * (size_t)lcap;
-    return 7 * k + (size_t)kPgoRec * ((size_t)E + 1) + 36 * k + 36 * k + 6 * k + 6 * k * nc + n * n + 8;
+    const size_t head = 7 * k + (size_t)kPgoRec * ((size_t)E + 1) + 36 * k + 36 * k + 6 * k;
+    // wide: the loop list (3 int32 a loop), one pass buffer, C, and the two capacitance vectors
+    if (wide) return head + 2 * (size_t)lcap + 6 * k * (size_t)kPgoThreads + n * n + 2 * n + 8;
+    return head + 6 * k * nc + n * n + 8;
 }
 
 SSF_DEV bool pgo_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }   // false for NaN
@@ -134,22 +153,151 @@ SSF_DEV double pgo_block_max(double v, double* lds) {
     return m;
 }
 
-__global__ __launch_bounds__(kPgoThreads) void k_pose_graph(
+// the right-hand side of one column of [ -g | A^T ] at node k: col 0 is -g, col 1 + 6 l + row is
+// row `row` of loop l's Jacobians (lrec: that loop's record), at its nodes li and lj
+struct PgoColumn {
+    int col, row, li, lj;
+    const double* lrec;
+    const double* GR;
+    SSF_DEV void operator()(int k, double b[6]) const {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            if (col == 0) b[r] = -GR[6 * (size_t)k + r];
+            else if (k == li) b[r] = lrec[6 + 6 * row + r];
+            else if (k == lj) b[r] = lrec[42 + 6 * row + r];
+            else b[r] = 0.0;
+        }
+    }
+};
+
+// T^-1 of one column on one lane: forward and back substitution through the block factors
+// (D: L_k with reciprocal diagonal, O: M_k), serial over the nodes.  The column lives at
+// z[(6 k + r) * zs]; the block factors are read one step ahead of their use.
+SSF_DEV void pgo_substitute(const double* D, const double* O, int K, double* z, size_t zs, const PgoColumn& rhs) {
+    double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // Ln / Mn: the blocks of the next step (L_k and the M that couples it to the step
+    // before), loaded while the current step computes
+    double Ln[36], Mn[36];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            if (c <= a) Ln[6 * a + c] = D[6 * a + c];
+            Mn[6 * a + c] = 0.0;
+        }
+    for (int k = 0; k < K; ++k) {
+        double Lk[36], M[36];
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                if (c <= a) Lk[6 * a + c] = Ln[6 * a + c];
+                M[6 * a + c] = Mn[6 * a + c];
+            }
+        if (k + 1 < K) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    if (c <= a) Ln[6 * a + c] = D[36 * (size_t)(k + 1) + 6 * a + c];
+                    Mn[6 * a + c] = O[36 * (size_t)(k) + 6 * a + c];
+                }
+        }
+        double b[6];
+        rhs(k, b);
+        if (k > 0) {
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) b[r] -= M[6 * r + c] * y[c];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            double s = b[r];
+#pragma unroll
+            for (int c = 0; c < r; ++c) s -= Lk[6 * r + c] * y[c];
+            y[r] = s * Lk[6 * r + r];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) z[(6 * (size_t)k + r) * zs] = y[r];
+    }
+    double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double bn[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            if (c <= a) Ln[6 * a + c] = D[36 * (size_t)(K - 1) + 6 * a + c];
+            Mn[6 * a + c] = 0.0;
+        }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) bn[r] = z[(6 * (size_t)(K - 1) + r) * zs];
+    for (int k = K - 1; k >= 0; --k) {
+        double Lk[36], M[36];
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                if (c <= a) Lk[6 * a + c] = Ln[6 * a + c];
+                M[6 * a + c] = Mn[6 * a + c];
+            }
+        double b[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) b[r] = bn[r];
+        if (k > 0) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) {
+                    if (c <= a) Ln[6 * a + c] = D[36 * (size_t)(k - 1) + 6 * a + c];
+                    Mn[6 * a + c] = O[36 * (size_t)(k - 1) + 6 * a + c];
+                }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) bn[r] = z[(6 * (size_t)(k - 1) + r) * zs];
+        }
+        if (k + 1 < K) {
+#pragma unroll
+            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) b[r] -= M[6 * c + r] * x[c];
+        }
+#pragma unroll
+        for (int r = 5; r >= 0; --r) {
+            double s = b[r];
+#pragma unroll
+            for (int c = r + 1; c < 6; ++c) s -= Lk[6 * c + r] * x[c];
+            x[r] = s * Lk[6 * r + r];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) z[(6 * (size_t)k + r) * zs] = x[r];
+    }
+}
+
+// The solver of both kernels.  kWide = false: up to kPgoNarrowLoops loop edges, every right-hand
+// side on a lane of its own, the loop list and the capacitance vectors in LDS.  kWide = true: up
+// to SSF_PGO_MAX_LOOPS, the columns of A^T in passes of kPgoThreads, everything sized by L in the
+// graph's scratch.  A work-group whose graph belongs to the other kernel returns at once.
+template <bool kWide>
+SSF_DEV void pgo_solve(
     const PgoGraph* __restrict__ desc, double* __restrict__ pose, const int32_t* __restrict__ node_off,
     const int32_t* __restrict__ edge_ij, const double* __restrict__ edge_meas,
     const double* __restrict__ edge_var, const int32_t* __restrict__ edge_off,
     const double* __restrict__ prior_pose, const double* __restrict__ prior_var, int max_iter,
     double func_tol, double* scratch, double* __restrict__ stats, double* __restrict__ cost_log) {
     __shared__ double red[kPgoThreads / 64];
-    __shared__ double va[kPgoMaxN], vb[kPgoMaxN];
+    __shared__ double va[kWide ? 1 : kPgoMaxN], vb[kWide ? 1 : kPgoMaxN];
     __shared__ int2 ij_s[kPgoTile];
     __shared__ double piv_s;
     __shared__ int bad_s, nloop_s, fail_s;
-    __shared__ int loop_e[SSF_PGO_MAX_LOOPS], loop_i[SSF_PGO_MAX_LOOPS], loop_j[SSF_PGO_MAX_LOOPS];
+    __shared__ int loop_e[kPgoNarrowLoops], loop_i[kPgoNarrowLoops], loop_j[kPgoNarrowLoops];
 
     const int g = blockIdx.x, tid = threadIdx.x;
     const PgoGraph G = desc[g];
+    if ((G.wide != 0) != kWide) return;
     const int K = G.K, E = G.E;
+    // wide: the loop list (edge, i, j) leads the graph's scratch
+    int32_t* LP = reinterpret_cast<int32_t*>(scratch + G.scratch_off);
+    const int lmax = kWide ? G.lcap : kPgoNarrowLoops;
     double* st = stats + (size_t)g * SSF_PGO_OUT_STRIDE;
     double* clog = cost_log ? cost_log + (size_t)g * (size_t)(max_iter + 1) : nullptr;
     const double kNaN = __builtin_nan("");
@@ -204,7 +352,10 @@ __global__ __launch_bounds__(kPgoThreads) void k_pose_graph(
                 const bool lp = e < E && i - j != 1 && j - i != 1;
                 const uint64_t m = __ballot(lp);
                 const int pos = cnt + __popcll(m & lanemask_lt());
-                if (lp && pos < SSF_PGO_MAX_LOOPS) { loop_e[pos] = e; loop_i[pos] = i; loop_j[pos] = j; }
+                if (lp && pos < lmax) {
+                    if constexpr (kWide) { LP[3 * pos] = e; LP[3 * pos + 1] = i; LP[3 * pos + 2] = j; }
+                    else { loop_e[pos] = e; loop_i[pos] = i; loop_j[pos] = j; }
+                }
                 cnt += __popcll(m);
             }
             if (tid == 0) nloop_s = cnt;
@@ -227,13 +378,16 @@ __global__ __launch_bounds__(kPgoThreads) void k_pose_graph(
 
     // ---- scratch of this graph
     const int NC = 6 * L + 1, n = 6 * L;
-    double* X = scratch + G.scratch_off;
+    double* X = scratch + G.scratch_off + (kWide ? 2 * (size_t)G.lcap : 0);
     double* REC = X + 7 * (size_t)K;
     double* D = REC + (size_t)kPgoRec * ((size_t)E + 1);
     double* O = D + 36 * (size_t)K;
     double* GR = O + 36 * (size_t)K;
     double* Z = GR + 6 * (size_t)K;
-    double* CM = Z + 6 * (size_t)K * (size_t)(6 * G.lcap + 1);
+    double* CM = Z + 6 * (size_t)K * (size_t)(kWide ? kPgoThreads : 6 * G.lcap + 1);
+    double* VA = CM + 36 * (size_t)G.lcap * (size_t)G.lcap;      // wide: u, then w
+    double* VB = VA + 6 * (size_t)G.lcap;
+    const size_t zs = kWide ? (size_t)kPgoThreads : (size_t)NC;  // stride of a column's entries in Z
     for (int k = tid; k < K; k += kPgoThreads) {
         double q[4];
         pgo_quat_unit(P + 7 * (size_t)k, q);
@@ -409,177 +563,205 @@ __global__ __launch_bounds__(kPgoThreads) void k_pose_graph(
         __syncthreads();
         if (fail_s) { status = SSF_PGO_NOT_PD; break; }
 
-        // -- T^-1 [ -g | A^T ]: one lane per column, serial over the nodes
-        if (tid < NC) {
-            const int col = tid, l = col > 0 ? (col - 1) / 6 : 0, row = col > 0 ? (col - 1) % 6 : 0;
-            const int li = col > 0 ? loop_i[l] : -1, lj = col > 0 ? loop_j[l] : -1;
-            const double* lrec = REC + (size_t)kPgoRec * (col > 0 ? loop_e[l] : 0);
-            double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            // Ln / Mn: the blocks of the next step (L_k and the M that couples it to the step
-            // before), loaded while the current step computes
-            double Ln[36], Mn[36];
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    if (c <= a) Ln[6 * a + c] = D[6 * a + c];
-                    Mn[6 * a + c] = 0.0;
-                }
-            for (int k = 0; k < K; ++k) {
-                double Lk[36], M[36];
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        if (c <= a) Lk[6 * a + c] = Ln[6 * a + c];
-                        M[6 * a + c] = Mn[6 * a + c];
-                    }
-                if (k + 1 < K) {
-#pragma unroll
-                    for (int a = 0; a < 6; ++a)
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) {
-                            if (c <= a) Ln[6 * a + c] = D[36 * (size_t)(k + 1) + 6 * a + c];
-                            Mn[6 * a + c] = O[36 * (size_t)(k) + 6 * a + c];
-                        }
-                }
-                double b[6];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) {
-                    if (col == 0) b[r] = -GR[6 * (size_t)k + r];
-                    else if (k == li) b[r] = lrec[6 + 6 * row + r];
-                    else if (k == lj) b[r] = lrec[42 + 6 * row + r];
-                    else b[r] = 0.0;
-                }
-                if (k > 0) {
-#pragma unroll
-                    for (int r = 0; r < 6; ++r)
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) b[r] -= M[6 * r + c] * y[c];
-                }
-#pragma unroll
-                for (int r = 0; r < 6; ++r) {
-                    double s = b[r];
-#pragma unroll
-                    for (int c = 0; c < r; ++c) s -= Lk[6 * r + c] * y[c];
-                    y[r] = s * Lk[6 * r + r];
-                }
-#pragma unroll
-                for (int r = 0; r < 6; ++r) Z[(6 * (size_t)k + r) * NC + col] = y[r];
-            }
-            double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            double bn[6];
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    if (c <= a) Ln[6 * a + c] = D[36 * (size_t)(K - 1) + 6 * a + c];
-                    Mn[6 * a + c] = 0.0;
-                }
-#pragma unroll
-            for (int r = 0; r < 6; ++r) bn[r] = Z[(6 * (size_t)(K - 1) + r) * NC + col];
-            for (int k = K - 1; k >= 0; --k) {
-                double Lk[36], M[36];
-#pragma unroll
-                for (int a = 0; a < 6; ++a)
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) {
-                        if (c <= a) Lk[6 * a + c] = Ln[6 * a + c];
-                        M[6 * a + c] = Mn[6 * a + c];
-                    }
-                double b[6];
-#pragma unroll
-                for (int r = 0; r < 6; ++r) b[r] = bn[r];
-                if (k > 0) {
-#pragma unroll
-                    for (int a = 0; a < 6; ++a)
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) {
-                            if (c <= a) Ln[6 * a + c] = D[36 * (size_t)(k - 1) + 6 * a + c];
-                            Mn[6 * a + c] = O[36 * (size_t)(k - 1) + 6 * a + c];
-                        }
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) bn[r] = Z[(6 * (size_t)(k - 1) + r) * NC + col];
-                }
-                if (k + 1 < K) {
-#pragma unroll
-                    for (int r = 0; r < 6; ++r)
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) b[r] -= M[6 * c + r] * x[c];
-                }
-#pragma unroll
-                for (int r = 5; r >= 0; --r) {
-                    double s = b[r];
-#pragma unroll
-                    for (int c = r + 1; c < 6; ++c) s -= Lk[6 * c + r] * x[c];
-                    x[r] = s * Lk[6 * r + r];
-                }
-#pragma unroll
-                for (int r = 0; r < 6; ++r) Z[(6 * (size_t)k + r) * NC + col] = x[r];
-            }
-        }
-        __syncthreads();
-
-        // -- Woodbury: C = I + A Z_A (column-major in CM), u = A z0, C w = u
-        if (L > 0) {
-            if (tid < n) {
-                const int l = tid / 6, row = tid % 6;
-                const double* lrec = REC + (size_t)kPgoRec * loop_e[l];
-                const double* zi = Z + 6 * (size_t)loop_i[l] * NC;
-                const double* zj = Z + 6 * (size_t)loop_j[l] * NC;
-                for (int b = 0; b <= n; ++b) {                 // b == 0: u; b >= 1: column b - 1
-                    double s = 0.0;
-                    for (int q = 0; q < 6; ++q)
-                        s += lrec[6 + 6 * row + q] * zi[(size_t)q * NC + b] + lrec[42 + 6 * row + q] * zj[(size_t)q * NC + b];
-                    if (b == 0) va[tid] = s;
-                    else CM[(size_t)(b - 1) * n + tid] = s + (b - 1 == tid ? 1.0 : 0.0);
-                }
-            }
-            __syncthreads();
-            for (int j = 0; j < n; ++j) {                      // Cholesky, one thread per row
-                double s = 0.0;
-                if (tid < n && tid >= j) {
-                    s = CM[(size_t)j * n + tid];
-                    for (int p = 0; p < j; ++p) s -= CM[(size_t)p * n + tid] * CM[(size_t)p * n + j];
-                    if (tid == j) piv_s = s;
-                }
-                __syncthreads();
-                const double piv = piv_s;
-                if (!(piv > 0.0) || !pgo_finite(piv)) { status = SSF_PGO_NOT_PD; break; }   // uniform
-                if (tid < n && tid >= j) CM[(size_t)j * n + tid] = tid == j ? sqrt(piv) : s / sqrt(piv);
-                __syncthreads();
-            }
-            if (status == SSF_PGO_NOT_PD) break;
-            for (int j = 0; j < n; ++j) {                      // forward: va -> vb
-                __syncthreads();
-                const double yj = va[j] / CM[(size_t)j * n + j];
-                if (tid == j) vb[j] = yj;
-                if (tid < n && tid > j) va[tid] -= CM[(size_t)j * n + tid] * yj;
-            }
-            for (int j = n - 1; j >= 0; --j) {                 // backward: vb -> va
-                __syncthreads();
-                const double xj = vb[j] / CM[(size_t)j * n + j];
-                if (tid == j) va[j] = xj;
-                if (tid < j) vb[tid] -= CM[(size_t)tid * n + j] * xj;
-            }
-            __syncthreads();
-        }
-
-        // -- dx = z0 - Z_A w (into column 0), its max-norm, then the retraction
         double mx = 0.0;
-        for (int k = tid; k < K; k += kPgoThreads)
-            for (int r = 0; r < 6; ++r) {
-                double* zr = Z + (6 * (size_t)k + r) * NC;
-                double s = zr[0];
-                for (int b = 0; b < n; ++b) s -= zr[1 + b] * va[b];
-                zr[0] = s;
-                mx = pgo_finite(s) ? fmax(mx, fabs(s)) : __builtin_inf();
+        if constexpr (!kWide) {
+            // -- T^-1 [ -g | A^T ]: one lane per column, serial over the nodes
+            if (tid < NC) {
+                const int col = tid, l = col > 0 ? (col - 1) / 6 : 0, row = col > 0 ? (col - 1) % 6 : 0;
+                const int li = col > 0 ? loop_i[l] : -1, lj = col > 0 ? loop_j[l] : -1;
+                const double* lrec = REC + (size_t)kPgoRec * (col > 0 ? loop_e[l] : 0);
+                pgo_substitute(D, O, K, Z + col, zs, PgoColumn{col, row, li, lj, lrec, GR});
             }
+            __syncthreads();
+
+            // -- Woodbury: C = I + A Z_A (column-major in CM), u = A z0, C w = u
+            if (L > 0) {
+                if (tid < n) {
+                    const int l = tid / 6, row = tid % 6;
+                    const double* lrec = REC + (size_t)kPgoRec * loop_e[l];
+                    const double* zi = Z + 6 * (size_t)loop_i[l] * NC;
+                    const double* zj = Z + 6 * (size_t)loop_j[l] * NC;
+                    for (int b = 0; b <= n; ++b) {                 // b == 0: u; b >= 1: column b - 1
+                        double s = 0.0;
+                        for (int q = 0; q < 6; ++q)
+                            s += lrec[6 + 6 * row + q] * zi[(size_t)q * NC + b] + lrec[42 + 6 * row + q] * zj[(size_t)q * NC + b];
+                        if (b == 0) va[tid] = s;
+                        else CM[(size_t)(b - 1) * n + tid] = s + (b - 1 == tid ? 1.0 : 0.0);
+                    }
+                }
+                __syncthreads();
+                for (int j = 0; j < n; ++j) {                      // Cholesky, one thread per row
+                    double s = 0.0;
+                    if (tid < n && tid >= j) {
+                        s = CM[(size_t)j * n + tid];
+                        for (int p = 0; p < j; ++p) s -= CM[(size_t)p * n + tid] * CM[(size_t)p * n + j];
+                        if (tid == j) piv_s = s;
+                    }
+                    __syncthreads();
+                    const double piv = piv_s;
+                    if (!(piv > 0.0) || !pgo_finite(piv)) { status = SSF_PGO_NOT_PD; break; }   // uniform
+                    if (tid < n && tid >= j) CM[(size_t)j * n + tid] = tid == j ? sqrt(piv) : s / sqrt(piv);
+                    __syncthreads();
+                }
+                if (status == SSF_PGO_NOT_PD) break;
+                for (int j = 0; j < n; ++j) {                      // forward: va -> vb
+                    __syncthreads();
+                    const double yj = va[j] / CM[(size_t)j * n + j];
+                    if (tid == j) vb[j] = yj;
+                    if (tid < n && tid > j) va[tid] -= CM[(size_t)j * n + tid] * yj;
+                }
+                for (int j = n - 1; j >= 0; --j) {                 // backward: vb -> va
+                    __syncthreads();
+                    const double xj = vb[j] / CM[(size_t)j * n + j];
+                    if (tid == j) va[j] = xj;
+                    if (tid < j) vb[tid] -= CM[(size_t)tid * n + j] * xj;
+                }
+                __syncthreads();
+            }
+
+            // -- dx = z0 - Z_A w (into column 0), its max-norm, then the retraction
+            for (int k = tid; k < K; k += kPgoThreads)
+                for (int r = 0; r < 6; ++r) {
+                    double* zr = Z + (6 * (size_t)k + r) * NC;
+                    double s = zr[0];
+                    for (int b = 0; b < n; ++b) s -= zr[1 + b] * va[b];
+                    zr[0] = s;
+                    mx = pgo_finite(s) ? fmax(mx, fabs(s)) : __builtin_inf();
+                }
+        } else {
+            // -- T^-1 [ -g | A^T ], kPgoThreads columns a pass, one lane per column.  A lane folds its
+            //    solved column into the capacitance matrix (column 0, z0 = T^-1 (-g), into u = A z0)
+            //    before the pass buffer is reused: T^-1 A^T is never held whole.  C = I + A Z_A is
+            //    column-major in CM.  A lane reads back only what it wrote itself: no barrier in here.
+            for (int c0 = 0; c0 < NC; c0 += kPgoThreads) {
+                const int col = c0 + tid;
+                if (col < NC) {
+                    const int l = col > 0 ? (col - 1) / 6 : 0, row = col > 0 ? (col - 1) % 6 : 0;
+                    const int li = col > 0 ? LP[3 * l + 1] : -1, lj = col > 0 ? LP[3 * l + 2] : -1;
+                    const double* lrec = REC + (size_t)kPgoRec * (col > 0 ? LP[3 * l] : 0);
+                    double* z = Z + tid;
+                    pgo_substitute(D, O, K, z, zs, PgoColumn{col, row, li, lj, lrec, GR});
+                    for (int m = 0; m < L; ++m) {                  // rows 6 m .. 6 m + 5 of A z
+                        const double* mrec = REC + (size_t)kPgoRec * LP[3 * m];
+                        const double* zi = z + 6 * (size_t)LP[3 * m + 1] * zs;
+                        const double* zj = z + 6 * (size_t)LP[3 * m + 2] * zs;
+                        double vi[6], vj[6];
+                        for (int q = 0; q < 6; ++q) { vi[q] = zi[(size_t)q * zs]; vj[q] = zj[(size_t)q * zs]; }
+                        for (int r = 0; r < 6; ++r) {
+                            double s = 0.0;
+                            for (int q = 0; q < 6; ++q) s += mrec[6 + 6 * r + q] * vi[q] + mrec[42 + 6 * r + q] * vj[q];
+                            if (col == 0) VA[6 * m + r] = s;
+                            else CM[(size_t)(col - 1) * n + 6 * m + r] = s + (col - 1 == 6 * m + r ? 1.0 : 0.0);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+
+            // -- Woodbury: C w = u by dense Cholesky, the rows strided over the threads (row
+            //    tid + q kPgoThreads in slot q), then dx = T^-1 (-g - A^T w).  Left-looking by
+            //    panels of kPgoPanel columns: a sweep over the columns left of the panel updates the
+            //    whole panel, so C is read n / kPgoPanel times, not n times.  A slot takes part while
+            //    any of its rows does (a uniform test); its rows above the diagonal read a clamped
+            //    address and their sums are never stored.
+            if (L > 0) {
+                for (int j0 = 0; j0 < n; j0 += kPgoPanel) {
+                    // t: the thread index made opaque, so that the row offsets below are not hoisted out
+                    // of the iteration loop into registers the substitution phases need
+                    int t = tid;
+                    asm volatile("" : "+v"(t));
+                    double acc[kPgoWideRows][kPgoPanel];
+#pragma unroll
+                    for (int q = 0; q < kPgoWideRows; ++q)
+#pragma unroll
+                        for (int b = 0; b < kPgoPanel; ++b) {
+                            const int r = t + q * kPgoThreads;
+                            acc[q][b] = r < n && r >= j0 && j0 + b < n ? CM[(size_t)(j0 + b) * n + r] : 0.0;
+                        }
+                    for (int p = 0; p < j0; ++p) {
+                        double cj[kPgoPanel];
+#pragma unroll
+                        for (int b = 0; b < kPgoPanel; ++b) cj[b] = CM[(size_t)p * n + min(j0 + b, n - 1)];
+#pragma unroll
+                        for (int q = 0; q < kPgoWideRows; ++q)
+                            if (q * kPgoThreads < n && (q + 1) * kPgoThreads > j0) {
+                                const double cr = CM[(size_t)p * n + min(t + q * kPgoThreads, n - 1)];
+#pragma unroll
+                                for (int b = 0; b < kPgoPanel; ++b) acc[q][b] -= cr * cj[b];
+                            }
+                    }
+#pragma unroll
+                    for (int b = 0; b < kPgoPanel; ++b) {          // the panel's own columns in turn
+                        const int j = j0 + b;
+                        if (j >= n) break;
+#pragma unroll
+                        for (int c = 0; c < b; ++c) {
+                            const double cjc = CM[(size_t)(j0 + c) * n + j];
+#pragma unroll
+                            for (int q = 0; q < kPgoWideRows; ++q) acc[q][b] -= acc[q][c] * cjc;
+                        }
+#pragma unroll
+                        for (int q = 0; q < kPgoWideRows; ++q)
+                            if (t + q * kPgoThreads == j) piv_s = acc[q][b];
+                        __syncthreads();
+                        const double piv = piv_s;
+                        if (!(piv > 0.0) || !pgo_finite(piv)) { status = SSF_PGO_NOT_PD; break; }   // uniform
+#pragma unroll
+                        for (int q = 0; q < kPgoWideRows; ++q) {
+                            const int r = t + q * kPgoThreads;
+                            acc[q][b] = r == j ? sqrt(piv) : acc[q][b] / sqrt(piv);
+                            if (r < n && r >= j) CM[(size_t)j * n + r] = acc[q][b];
+                        }
+                        __syncthreads();
+                    }
+                    if (status == SSF_PGO_NOT_PD) break;
+                }
+                if (status == SSF_PGO_NOT_PD) break;
+                for (int j = 0; j < n; ++j) {                      // forward: VA -> VB
+                    __syncthreads();
+                    const double yj = VA[j] / CM[(size_t)j * n + j];
+                    if (tid == j % kPgoThreads) VB[j] = yj;
+                    for (int r = tid; r < n; r += kPgoThreads)
+                        if (r > j) VA[r] -= CM[(size_t)j * n + r] * yj;
+                }
+                for (int j = n - 1; j >= 0; --j) {                 // backward: VB -> VA
+                    __syncthreads();
+                    const double xj = VB[j] / CM[(size_t)j * n + j];
+                    if (tid == j % kPgoThreads) VA[j] = xj;
+                    for (int r = tid; r < j; r += kPgoThreads) VB[r] -= CM[(size_t)r * n + j] * xj;
+                }
+                __syncthreads();
+                // g + A^T w at the loop nodes in loop order, then one more column: -(g + A^T w)
+                if (tid == 0) {
+                    for (int m = 0; m < L; ++m) {
+                        const double* mrec = REC + (size_t)kPgoRec * LP[3 * m];
+                        double* gi = GR + 6 * (size_t)LP[3 * m + 1];
+                        double* gj = GR + 6 * (size_t)LP[3 * m + 2];
+                        for (int q = 0; q < 6; ++q) {
+                            double si = 0.0, sj = 0.0;
+                            for (int r = 0; r < 6; ++r) {
+                                si += mrec[6 + 6 * r + q] * VA[6 * m + r];
+                                sj += mrec[42 + 6 * r + q] * VA[6 * m + r];
+                            }
+                            gi[q] += si;
+                            gj[q] += sj;
+                        }
+                    }
+                    pgo_substitute(D, O, K, Z, zs, PgoColumn{0, 0, -1, -1, REC, GR});
+                }
+                __syncthreads();
+            }
+            for (int k = tid; k < K; k += kPgoThreads)
+                for (int r = 0; r < 6; ++r) {
+                    const double s = Z[(6 * (size_t)k + r) * zs];
+                    mx = pgo_finite(s) ? fmax(mx, fabs(s)) : __builtin_inf();
+                }
+        }
         dxmax = pgo_block_max(mx, red);
         if (!pgo_finite(dxmax)) { status = SSF_PGO_NOT_PD; break; }
         for (int k = tid; k < K; k += kPgoThreads) {
             double d[6];
-            for (int r = 0; r < 6; ++r) d[r] = Z[(6 * (size_t)k + r) * NC];
+            for (int r = 0; r < 6; ++r) d[r] = Z[(6 * (size_t)k + r) * zs];
             double* x = X + 7 * (size_t)k;
             const double q[4] = {x[0], x[1], x[2], x[3]};
             double R[9];
@@ -609,16 +791,43 @@ __global__ __launch_bounds__(kPgoThreads) void k_pose_graph(
     }
 }
 
-hipError_t launch_pose_graph(hipStream_t s, int n_graphs, const PgoGraph* desc, double* pose,
-                             const int32_t* node_off, const int32_t* edge_ij, const double* edge_meas,
-                             const double* edge_var, const int32_t* edge_off, const double* prior_pose,
-                             const double* prior_var, int max_iter, double func_tol, double* scratch,
-                             double* stats, double* cost_log) {
+#define SSF_PGO_KERNEL_ARGS                                                                              \
+    const PgoGraph *__restrict__ desc, double *__restrict__ pose, const int32_t *__restrict__ node_off,  \
+        const int32_t *__restrict__ edge_ij, const double *__restrict__ edge_meas,                       \
+        const double *__restrict__ edge_var, const int32_t *__restrict__ edge_off,                       \
+        const double *__restrict__ prior_pose, const double *__restrict__ prior_var, int max_iter,       \
+        double func_tol, double *scratch, double *__restrict__ stats, double *__restrict__ cost_log
+
+__global__ __launch_bounds__(kPgoThreads) void k_pose_graph(SSF_PGO_KERNEL_ARGS) {
+    pgo_solve<false>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
+                     max_iter, func_tol, scratch, stats, cost_log);
+}
+
+__global__ __launch_bounds__(kPgoThreads) void k_pose_graph_wide(SSF_PGO_KERNEL_ARGS) {
+    pgo_solve<true>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
+                    max_iter, func_tol, scratch, stats, cost_log);
+}
+
+// Both kernels run over every graph of the batch; a work-group returns at once when its graph
+// (PgoGraph::wide) is the other kernel's.  A kernel with no graph of its own is not launched.
+hipError_t launch_pose_graph(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide, const PgoGraph* desc,
+                             double* pose, const int32_t* node_off, const int32_t* edge_ij,
+                             const double* edge_meas, const double* edge_var, const int32_t* edge_off,
+                             const double* prior_pose, const double* prior_var, int max_iter,
+                             double func_tol, double* scratch, double* stats, double* cost_log) {
     if (n_graphs <= 0) return hipSuccess;
-    kmark(s, "k_pose_graph");
-    hipLaunchKernelGGL(k_pose_graph, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose, node_off, edge_ij,
-                       edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter, func_tol, scratch,
-                       stats, cost_log);
+    if (any_narrow) {
+        kmark(s, "k_pose_graph");
+        hipLaunchKernelGGL(k_pose_graph, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose, node_off, edge_ij,
+                           edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter, func_tol, scratch,
+                           stats, cost_log);
+    }
+    if (any_wide) {
+        kmark(s, "k_pose_graph_wide");
+        hipLaunchKernelGGL(k_pose_graph_wide, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose, node_off,
+                           edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter, func_tol,
+                           scratch, stats, cost_log);
+    }
     return hipGetLastError();
 }
 

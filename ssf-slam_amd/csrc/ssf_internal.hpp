@@ -303,10 +303,12 @@ struct PgoGraph {             // one per graph, built on the host from the host 
     int64_t scratch_off;      // this graph's piece of the context scratch, in doubles
     int32_t node0, K, edge0, E;
     int32_t lcap;             // min(max(E - (K - 1), 0), SSF_PGO_MAX_LOOPS): loop edges it has room for
-    int32_t pad;
+    int32_t wide;             // pgo_graph_wide(K, E): solved by k_pose_graph_wide
 };
-size_t pgo_graph_doubles(int K, int E, int lcap);
-hipError_t launch_pose_graph(hipStream_t s, int n_graphs, const PgoGraph* desc, double* pose,
+bool pgo_graph_wide(int K, int E);      // more than 32 edges beyond K - 1: it may hold more than 32 loops
+size_t pgo_graph_doubles(int K, int E, int lcap, bool wide);
+hipError_t launch_pose_graph(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
+                             const PgoGraph* desc, double* pose,
                              const int32_t* node_off, const int32_t* edge_ij, const double* edge_meas,
                              const double* edge_var, const int32_t* edge_off, const double* prior_pose,
                              const double* prior_var, int max_iter, double func_tol, double* scratch,

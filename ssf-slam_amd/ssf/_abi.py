@@ -59,7 +59,7 @@ ICP_STATES = {0: "not_converged", 1: "iterations", 2: "transform", 3: "abs_mse",
               5: "no_correspondences"}
 
 
-PGO_MAX_LOOPS, PGO_MAX_ITER, PGO_OUT_STRIDE = 32, 1024, 8
+PGO_MAX_LOOPS, PGO_MAX_ITER, PGO_OUT_STRIDE = 256, 1024, 8
 PGO_OUT = dict(STATUS=0, ITERATIONS=1, COST0=2, COST=3, DX=4, LOOPS=5)
 PGO_OK, PGO_CONVERGED, PGO_EMPTY, PGO_BAD_INPUT, PGO_TOO_MANY_LOOPS, PGO_NOT_PD = range(6)
 PGO_STATUS = {0: "ok", 1: "converged", 2: "empty", 3: "bad_input", 4: "too_many_loops", 5: "not_pd"}

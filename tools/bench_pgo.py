@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Time ssf_pose_graph_batch (pose_graph.hip) on two shapes: many medium graphs in one launch
-(G=256, K=512, L=8: the bench configuration's 256 sequences per GPU closing a loop together)
-and one long graph at the loop limit (G=1, K=4096, L=32).
+"""Time ssf_pose_graph_batch (pose_graph.hip): many medium graphs in one launch (G=256, K=512,
+L=8: the bench configuration's 256 sequences per GPU closing a loop together), one long graph at
+the limit of the lane-per-column kernel (G=1, K=4096, L=32), and graphs of the wide kernel: the
+long graph at L = 33, 64 and 256 and a batch (G=64, K=512) at L = 64, each with its ratio to
+the L = 32 line of the same G and K (`--only` picks lines by name).
 
 HIP events around the ABI call on the current stream, one synchronise per sample, warm-up
 first, median of --runs samples (>= 20).  Every sample starts from the same drifted poses (a
@@ -18,7 +20,10 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "ssf-slam_amd"))
 
-SHAPES = [dict(name="batch", G=256, K=512, L=8), dict(name="long", G=1, K=4096, L=32)]
+SHAPES = [dict(name="batch", G=256, K=512, L=8), dict(name="long", G=1, K=4096, L=32),
+          dict(name="long_l33", G=1, K=4096, L=33, ref="long"), dict(name="long_l64", G=1, K=4096, L=64, ref="long"),
+          dict(name="long_l256", G=1, K=4096, L=256, ref="long"),
+          dict(name="batch64_l32", G=64, K=512, L=32), dict(name="batch64_l64", G=64, K=512, L=64, ref="batch64_l32")]
 
 
 def circle(K, L, seed):
@@ -61,7 +66,11 @@ def main():
     ap.add_argument("--runs", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "pgo_bench.json"))
+    ap.add_argument("--only", default="", help="comma-separated line names (default: all)")
     a = ap.parse_args()
+    only = [n for n in a.only.split(",") if n]
+    if any(n not in [sh["name"] for sh in SHAPES] for n in only):
+        ap.error(f"--only: unknown line in {only}")
     if a.runs < 20:
         ap.error("--runs must be at least 20")
     import torch
@@ -73,7 +82,7 @@ def main():
     prm = _abi.PgoParams()
     L.ssf_pgo_params_default(C.byref(prm))
     results = []
-    for sh in SHAPES:
+    for sh in [sh for sh in SHAPES if not only or sh["name"] in only]:
         G, K, nl = sh["G"], sh["K"], sh["L"]
         gs = [circle(K, nl, 100 + (g % 8)) for g in range(min(G, 8))]
         gs = [gs[g % len(gs)] for g in range(G)]
@@ -111,7 +120,10 @@ def main():
                    max_ms=float(np.max(ms)), iterations=sorted(set(int(v) for v in st[:, 1])),
                    status=[_abi.PGO_STATUS[s] for s in status], cost0=float(st[0, 2]), cost=float(st[0, 3]),
                    max_iter=prm.max_iter, func_tol=prm.func_tol)
-        print(json.dumps(row))
+        ref = [r for r in results if r["name"] == sh.get("ref")]
+        if ref:                                      # against the L = 32 line of the same G and K
+            row["ratio_to_l32"] = row["median_ms"] / ref[0]["median_ms"]
+        print(json.dumps(row), flush=True)
         if any(s not in (_abi.PGO_OK, _abi.PGO_CONVERGED) for s in status):
             raise SystemExit(f"{sh['name']}: a graph failed: {row['status']}")
         results.append(row)
