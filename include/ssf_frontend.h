@@ -428,6 +428,49 @@ int32_t ssf_set_mask_schedule(ssf_ctx* ctx, const int32_t* d_order, int32_t n_or
 int32_t ssf_rng_seed(ssf_ctx* ctx, uint32_t seed);
 
 /* ---------------------------------------------------------------------------------------
+ * The ASF loader's subsample: replaces the rm_ground cut, hybrid_sample_points and the
+ * np.random.choice to nb_points of scripts/ActiveSceneFlow/utils/datasets/carla.py:179-200,
+ * 236-250, 274-285 for F clouds in one launch.  The draw is defined here, not
+ * numpy's MT19937 stream: with F(z) the SplitMix64 finaliser, g = 0x9E3779B97F4A7C15,
+ *   s(stream)      = F(F(F(seed + g) + tag) + stream)
+ *   key(stream, i) = (F(s(stream) + (i + 1) g) >> 32) >> (32 - key_bits)     i: index in the frame
+ * so a frame's result depends on (seed, tag, its own points) only.
+ *   d_pts [total, point_stride] f32 (point_stride >= 3), d_frame_off / h_frame_off [F + 1] int64
+ *                 (device and host copies; a frame holds at most SSF_SAMPLE_MAX_POINTS points)
+ *   d_class       nullable uint8 per point: 0 background, else foreground (the quota needs it)
+ *   nb            points to return per frame, 1 .. SSF_SAMPLE_MAX_NB
+ *   use_z, z_min  use_z != 0: the survivors are the points with !(z < z_min) (carla.py:237: a NaN
+ *                 z survives); else every point
+ *   quota         -1: off.  >= 0: k_fg = min(foreground survivors, quota, nb) smallest-key
+ *                 foreground survivors first, then the nb - k_fg smallest-key background survivors;
+ *                 SSF_SAMPLE_SHORT when the background holds fewer (the reference's choice raises)
+ *   h_tag         nullable host [F] uint64 (read during the call): NULL = the frame's position
+ *   key_bits      1 .. 32 (32: the definition; fewer truncate the keys of stream 0, so that ties
+ *                 and the index tie-break occur at small sizes)
+ * Without quota: survivors n > nb -> the nb survivors smallest in (key(0, i), i), ascending in that
+ * order (a uniformly random ordered sample without replacement); 1 <= n <= nb -> slot j is the
+ * survivor of rank (key(1, j) * n) >> 32 in index order, key_bits taken as 32 (with replacement:
+ * the reference resamples unless nb < n, carla.py:274-277).  n == 0 -> SSF_SAMPLE_EMPTY.  A frame
+ * whose status is not SSF_SAMPLE_OK has its d_idx / d_xyz rows zero-filled; other frames are not
+ * affected.
+ *   d_idx [F, nb] int32 index within the frame;  d_xyz [F, 3, nb] f32 nullable, channel-major
+ *   (TFlow's input layout);  d_n [F] int32 survivors;  d_status [F] int32 SSF_SAMPLE_*.
+ * Asynchronous on stream.  SSF_E_ARG before any HIP call: null context or pointer (d_pts may be
+ * NULL for a batch that holds no point), n_frames < 0,
+ * nb, key_bits or point_stride out of range, quota < -1, quota >= 0 without d_class, offsets that
+ * decrease, a frame above SSF_SAMPLE_MAX_POINTS. */
+#define SSF_SAMPLE_MAX_NB 8192
+#define SSF_SAMPLE_MAX_POINTS (1 << 24)
+#define SSF_SAMPLE_TAG_CHUNK 256   /* frames per launch when h_tag is given */
+enum { SSF_SAMPLE_OK = 0, SSF_SAMPLE_EMPTY = -1, SSF_SAMPLE_SHORT = -2 };
+int32_t ssf_subsample_batch(ssf_ctx* ctx, void* stream, int32_t n_frames, const float* d_pts,
+                            int32_t point_stride, const int64_t* d_frame_off,
+                            const int64_t* h_frame_off, const uint8_t* d_class, int32_t nb,
+                            float z_min, int32_t use_z, int32_t quota, uint64_t seed,
+                            const uint64_t* h_tag, int32_t key_bits, int32_t* d_idx, float* d_xyz,
+                            int32_t* d_n, int32_t* d_status);
+
+/* ---------------------------------------------------------------------------------------
  * lidarOdometry.cpp (SSF path): frameRegistration() (src/lidarOdometry.cpp:145-159) ingests
  * [t, q] and publishResult() (:80-83) accumulates.  Batched prefix product over a sequence of
  * n relative poses (7 doubles each, q xyzw + t): d_abs[i] = d_abs[i-1] * d_rel[i], seeded with

@@ -897,6 +897,38 @@ int32_t ssf_kabsch_f32_batch(ssf_ctx* c, void* stream, int32_t n_frames, const f
     return SSF_OK;
 }
 
+int32_t ssf_subsample_batch(ssf_ctx* c, void* stream, int32_t n_frames, const float* d_pts,
+                            int32_t point_stride, const int64_t* d_frame_off,
+                            const int64_t* h_frame_off, const uint8_t* d_class, int32_t nb,
+                            float z_min, int32_t use_z, int32_t quota, uint64_t seed,
+                            const uint64_t* h_tag, int32_t key_bits, int32_t* d_idx, float* d_xyz,
+                            int32_t* d_n, int32_t* d_status) {
+    if (!c) return SSF_E_ARG;
+    if (n_frames < 0 || nb < 1 || nb > SSF_SAMPLE_MAX_NB || point_stride < 3 || key_bits < 1 ||
+        key_bits > 32 || quota < -1 || (quota >= 0 && !d_class))
+        return fail(c, SSF_E_ARG, "subsample_batch: bad arguments (1 <= nb <= 8192, stride >= 3, "
+                                  "1 <= key_bits <= 32, quota >= -1 and a class array with a quota)");
+    if (n_frames > 0 && (!d_frame_off || !h_frame_off || !d_idx || !d_n || !d_status))
+        return fail(c, SSF_E_ARG, "subsample_batch: null pointer");
+    if (n_frames == 0) return SSF_OK;
+    if (!d_pts && h_frame_off[n_frames] != h_frame_off[0])      // a batch of empty frames has no points
+        return fail(c, SSF_E_ARG, "subsample_batch: null pointer");
+    for (int k = 0; k < n_frames; ++k) {
+        const int64_t m = h_frame_off[k + 1] - h_frame_off[k];
+        if (m < 0 || h_frame_off[k] < 0) return fail(c, SSF_E_ARG, "subsample_batch: offsets not monotone");
+        if (m > (int64_t)SSF_SAMPLE_MAX_POINTS)
+            return fail(c, SSF_E_ARG, "subsample_batch: a frame holds more than 2^24 points");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    ProfScope prof(c, stream);
+    hipError_t e = ssf::launch_subsample(s, n_frames, d_pts, point_stride, d_frame_off, d_class, nb,
+                                         z_min, use_z, quota, seed, h_tag, key_bits, d_idx, d_xyz,
+                                         d_n, d_status);
+    if (e != hipSuccess) return hip_fail(c, e, "subsample launch");
+    return SSF_OK;
+}
+
 int32_t ssf_accumulate_sequence(ssf_ctx* c, void* stream, int32_t n, const double* d_rel,
                                 const double* h_start, double* d_abs) {
     if (!c) return SSF_E_ARG;

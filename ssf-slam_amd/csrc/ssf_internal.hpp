@@ -267,6 +267,12 @@ int mask_pose_slots(int device);
 hipError_t launch_kabsch_f32(hipStream_t s, int n_frames, const float* src, const float* dst,
                              const float* flow, const int64_t* frame_off, const uint8_t* mask,
                              int reflection, int keep_failures, double* out);
+// ---- launcher (subsample.hip): the seeded subsample of ssf_subsample_batch, one work-group per
+// frame; h_tag (host, nullable) rides in the kernel arguments.
+hipError_t launch_subsample(hipStream_t s, int n_frames, const float* pts, int stride,
+                            const int64_t* frame_off, const uint8_t* cls, int nb, float z_min,
+                            int use_z, int quota, uint64_t seed, const uint64_t* h_tag, int key_bits,
+                            int32_t* idx, float* xyz, int32_t* n_out, int32_t* status);
 size_t mask_sync_bytes(int n_frames);
 size_t mask_parts_bytes(int n_frames, int G);
 

@@ -12,7 +12,8 @@ from .map_cloud import MapCloud  # noqa: F401  (mapOptmization's accumulated map
 from . import pointnet2  # noqa: F401  (TFlow point-set operators: pointutils surface)
 from . import tflow  # noqa: F401  (the TFlow network: cost volume, warping, flow regressor)
 from .tflow import CostVolume, PointWarping, RefineFlowRegressor, TFlow  # noqa: F401
+from . import asf  # noqa: F401  (the ActiveSceneFlow chain: subsample, TFlow, mask, pose)
 
 __all__ = ["Frontend", "PlaneBatch", "frame_offsets", "identity_poses", "register_plan", "SSFError",
            "mask_and_pose", "slove_RT_by_SVD", "loop", "MapCloud", "pointnet2"]
-__all__ += ["tflow", "CostVolume", "PointWarping", "RefineFlowRegressor", "TFlow"]
+__all__ += ["tflow", "CostVolume", "PointWarping", "RefineFlowRegressor", "TFlow", "asf"]

@@ -40,8 +40,11 @@ EXPORTS = [
     "ssf_edge_config_default", "ssf_set_edge_config", "ssf_extract_features_batch",
     "ssf_edge_table_batch", "ssf_register_batch_edges", "ssf_kabsch_f32_batch",
     "ssf_set_mask_schedule", "ssf_register_plan", "ssf_pgo_params_default", "ssf_pose_graph_batch",
-    "ssf_transform_clouds_batch",
+    "ssf_transform_clouds_batch", "ssf_subsample_batch",
 ]
+# ssf_subsample_batch: limits and per-frame status codes
+SAMPLE_MAX_NB, SAMPLE_MAX_POINTS = 8192, 1 << 24
+SAMPLE_OK, SAMPLE_EMPTY, SAMPLE_SHORT = 0, -1, -2
 # Every symbol include/ssf_pointnet2.h declares (TFlow point-set operators).
 PN2_EXPORTS = [
     "ssf_pn2_last_error", "ssf_pn2_furthest_point_sample", "ssf_pn2_knn", "ssf_pn2_three_nn",
@@ -171,6 +174,9 @@ def lib():
     L.ssf_mask_pose_batch_f64.restype = i32
     L.ssf_kabsch_f32_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp]
     L.ssf_kabsch_f32_batch.restype = i32
+    L.ssf_subsample_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, C.c_float, i32, i32,
+                                      C.c_uint64, vp, i32, vp, vp, vp, vp]
+    L.ssf_subsample_batch.restype = i32
     L.ssf_edge_config_default.argtypes = [i32, C.POINTER(EdgeConfig)]
     L.ssf_edge_config_default.restype = i32
     L.ssf_set_edge_config.argtypes = [vp, C.POINTER(EdgeConfig)]

@@ -86,6 +86,77 @@ def _ros_pointcloud_odometry(a, mode):
         rate.sleep()
 
 
+ASF_MODES = {  # script -> (mask mode, launch graph of the offline replay)
+    "main_sju_occ_ros.py": ("gmm", "noSeg_ActiveSceneFlow"),
+    "main_sju_occ_addSeg_ros.py": ("gt", "Seg_ActiveSceneFlow"),
+}
+
+
+def active_scene_flow_main(script: str, argv=None):
+    """The `type=` targets of run_noSeg_ActiveSceneFlow.launch / run_Seg_ActiveSceneFlow.launch
+    (main_sju_occ_ros.py:495-566, main_sju_occ_addSeg_ros.py): params ~DATASET_PATH and
+    ~MODEL_PATH (a TFlow checkpoint; --model_path as the reference's argument)."""
+    mode, launch = ASF_MODES[script]
+    ap = _parser(script)
+    ap.add_argument("--dataset", default=None,
+                    help="offline: replay this DATASET_PATH through the whole run_%s.launch graph" % launch)
+    ap.add_argument("--model_path", "--model-path", dest="model_path", default=None,
+                    help="TFlow checkpoint (the ~MODEL_PATH parameter under ROS)")
+    ap.add_argument("--result", default=None, help="offline: RESULT_PATH TUM file (appended)")
+    ap.add_argument("--num_points", "--n-points", dest="n_points", type=int, default=8192)
+    ap.add_argument("--seed", type=int, default=1234, help="the sampler's and the GMM's seed")
+    ap.add_argument("--rate", type=float, default=10.0)
+    a, _ = ap.parse_known_args(argv)
+    from . import rosbridge
+    if a.dataset is None and rosbridge.available():
+        return _ros_active_scene_flow(a, mode)
+    if a.dataset is None:
+        raise SystemExit(f"{script}: rospy is not importable; pass --dataset DATASET_PATH and "
+                         f"--model_path CHECKPOINT to replay the run_{launch}.launch graph offline")
+    if a.model_path is None:
+        raise SystemExit(f"{script}: --model_path CHECKPOINT is needed (no trained weights ship with "
+                         f"the project)")
+    import torch
+    from .nodes import run_sequence
+    torch.cuda.set_device(a.device)
+    res = run_sequence(a.dataset, a.result, n_rows=a.rows, seed=a.seed, launch=launch, rate_hz=a.rate,
+                       weights=a.model_path, n_points=a.n_points)
+    print(json.dumps({"script": script, "launch": launch, "frames": len(res["stamps"]),
+                      "frame_odom1": res["odom1"].tolist(), "frame_odom2": res["odom2"].tolist()}))
+    return res
+
+
+def _ros_active_scene_flow(a, mode):
+    import torch
+    from . import io as sio
+    from . import rosbridge
+    from .asf import ActiveSceneFlowNode
+    from .nodes import _asf_net
+    rospy = rosbridge.require()[0]
+    rospy.init_node("velodyne_points_odometry_node", anonymous=True)
+    pub = rosbridge.RosPublisher(["/velodyne_points", "/frame_odom1"])
+    rate = rospy.Rate(a.rate)
+    root = rospy.get_param("~DATASET_PATH") if rospy.has_param("~DATASET_PATH") else "."
+    model = rospy.get_param("~MODEL_PATH") if rospy.has_param("~MODEL_PATH") else a.model_path
+    torch.cuda.set_device(a.device)
+    dev = torch.device("cuda", a.device)
+    node = ActiveSceneFlowNode(pub, _asf_net(model, a.n_points, dev), mode=mode, n_points=a.n_points,
+                               seed=a.seed, device=dev)
+    rospy.loginfo("\033[1;32m----> ActiveSceneFlow Started.\033[0m")
+    for path in sio.sequence_files(root):
+        if rospy.is_shutdown():
+            break
+        rospy.loginfo(path)
+        import numpy as np
+        with np.load(path, allow_pickle=False) as z:
+            fr = {k: np.ascontiguousarray(z[k], dtype=np.float32)
+                  for k in ("pos1", "pos2", "s_fg_mask", "t_fg_mask") if k in z.files}
+        now = rospy.Time.now()
+        node.on_pair(fr["pos1"], fr["pos2"], (now.secs, now.nsecs), fg1=fr.get("s_fg_mask"),
+                     fg2=fr.get("t_fg_mask"))
+        rate.sleep()
+
+
 NODES = {  # executable -> (ROS node name, reference main)
     "frameFeature": ("frameFeature", "src/frameFeature.cpp:154-168"),
     "lidarOdometry_onlyPC": ("LidarOdometry", "src/lidarOdometry_onlyPC.cpp:313-334"),

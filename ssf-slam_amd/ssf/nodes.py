@@ -17,6 +17,10 @@ way `launch/*.launch` wires the nodes and writes the odometry as a TUM trajector
       second plane cloud on and accumulates it -> /frame_odom2, /frame_odom_path2,
       /plane_frame_cloud2 (no registration: the pose is the SSF Kabsch pose)
 
+The data-source node of the two ActiveSceneFlow launches (pairs of scans through the sampler,
+TFlow, the mask and the float32 Kabsch) is ssf.asf.ActiveSceneFlowNode; run_sequence builds it
+for launch "noSeg_ActiveSceneFlow" / "Seg_ActiveSceneFlow".
+
 rospy, sensor_msgs and nav_msgs are not in this image: messages are the plain stand-ins of
 `ssf.io` / below, and a `Bus` delivers them in-process.  Subscribed callbacks are duck-typed
 (any object with the sensor_msgs/PointCloud2 attributes works), so wiring a node to rospy is
@@ -322,24 +326,59 @@ LAUNCH_GRAPHS = {
     "onlyPC": ("none", "registration", ("pos1",)),             # run_onlyPC.launch:7-15
     "noSeg": ("gmm", "ingest", ("pos1", "gt")),                 # run_noSeg.launch:7-16
     "Seg": ("gt", "ingest", ("pos1", "gt", "s_fg_mask")),       # run_Seg.launch:7-16
+    # the ActiveSceneFlow launches (data source: ssf.asf.ActiveSceneFlowNode on pairs of scans); a
+    # fourth entry: the npz keys that are read when the files carry them
+    "noSeg_ActiveSceneFlow": ("gmm", "ingest", ("pos1", "pos2"),            # run_noSeg_ActiveSceneFlow.launch
+                              ("gt", "s_fg_mask", "t_fg_mask")),
+    "Seg_ActiveSceneFlow": ("gt", "ingest", ("pos1", "pos2", "s_fg_mask"),  # run_Seg_ActiveSceneFlow.launch
+                            ("gt", "t_fg_mask")),
 }
+ASF_LAUNCHES = ("noSeg_ActiveSceneFlow", "Seg_ActiveSceneFlow")
+
+
+def _npz_keys(root, keys, optional):
+    """keys plus the optional ones the first file of the sequence carries"""
+    files = sio.sequence_files(root)
+    if not files:
+        return tuple(keys)
+    with np.load(files[0], allow_pickle=False) as z:
+        return tuple(keys) + tuple(k for k in optional if k in z.files)
+
+
+def _asf_net(weights, n_points, device):
+    """the TFlow of an ASF launch: a ready module, or a checkpoint path loaded into a new one"""
+    from .asf import load_checkpoint
+    from .tflow import TFlow
+    if weights is None:
+        raise ValueError("an ActiveSceneFlow launch needs the network's weights: pass weights= (a "
+                         "checkpoint path or a TFlow); no trained weights ship with the project")
+    if isinstance(weights, torch.nn.Module):
+        return weights
+    return load_checkpoint(TFlow(npoint=n_points), weights).to(device)
 
 
 def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, device=None,
                  solver: str = "ceres_lm", max_iter: int | None = None, seed: int | None = None,
                  rate_hz: float = 10.0, launch: str = "onlyPC", map_tum_path: str | None = None,
-                 truncate_results: bool = False, map_optimize: bool = False, map_cloud: bool = False):
+                 truncate_results: bool = False, map_optimize: bool = False, map_cloud: bool = False,
+                 weights=None, n_points: int = 8192):
     """Replay a DATASET_PATH directory through the node graph of launch/run_<launch>.launch:
       onlyPC: PointCloudOdometry_onlyPC -> frameFeature -> lidarOdometry_onlyPC (registration)
       noSeg:  PointCloudOdometry_noSeg (GMM mask + Kabsch -> /frame_odom1) -> frameFeature ->
               lidarOdometry (pose ingest + accumulation)
       Seg:    PointCloudOdometry (ground-truth mask s_fg_mask == 0) -> same as noSeg
+      noSeg_ActiveSceneFlow / Seg_ActiveSceneFlow: ssf.asf.ActiveSceneFlowNode (subsample to
+              n_points, TFlow with `weights` -- a checkpoint path or a ready TFlow --, GMM /
+              ground-truth mask on the network's flow, float32 Kabsch -> /frame_odom1) -> same
+              as noSeg; npz keys pos1, pos2 (+ gt, s_fg_mask, t_fg_mask when present); the sampler
+              and the GMM take `seed` (default 1234)
     plus mapOptmization when `map_tum_path` is given (map_optimize: with the GPU pose-graph
     optimisation of its loop closures).  Stamps are synthetic and monotone (frame k
     at k / rate_hz; the reference uses wall-clock ros::Time::now()).  The /frame_odom2 poses are
     appended to `tum_path` as TUM lines (like the reference, an existing file is extended unless
     truncate_results=True).
     -> dict(odom1 [F, 7] f64 [t, q] (empty for onlyPC), odom2 [F-1, 7] f64 [t, q], stamps, loops;
+    an ASF launch on files with gt also flow_metrics, one dict per pair;
     with map_optimize also optimization (the last solve) and key_poses; with map_cloud (needs
     map_tum_path) also map_cloud, the final 0.4 m map as float32 [M, 4], map_cloud_published,
     the number of /sum_map_cloud_res3 messages, and map_cloud_keyframes)"""
@@ -347,10 +386,18 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
         raise ValueError(f"launch {launch!r}: one of {sorted(LAUNCH_GRAPHS)}")
     if map_cloud and map_tum_path is None:
         raise ValueError("map_cloud needs mapOptmization in the graph: pass map_tum_path")
-    src_mode, odo_kind, keys = LAUNCH_GRAPHS[launch]
+    src_mode, odo_kind, keys = LAUNCH_GRAPHS[launch][:3]
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     bus = Bus()
-    pco = PointCloudOdometryNode(bus.publish, device=dev, seed=seed, mode=src_mode)
+    asf = launch in ASF_LAUNCHES
+    if asf:
+        from .asf import ActiveSceneFlowNode
+        net = _asf_net(weights, n_points, dev)
+        keys = _npz_keys(root, keys, LAUNCH_GRAPHS[launch][3])
+        pco = ActiveSceneFlowNode(bus.publish, net, mode=src_mode, n_points=n_points, device=dev,
+                                  **({} if seed is None else dict(seed=seed)))
+    else:
+        pco = PointCloudOdometryNode(bus.publish, device=dev, seed=seed, mode=src_mode)
     ff = FrameFeatureNode(bus.publish, n_rows=n_rows, device=dev)
     if odo_kind == "registration":
         lo = LidarOdometryNode(bus.publish, n_rows=n_rows, device=dev, solver=solver, max_iter=max_iter)
@@ -386,15 +433,24 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
         bus.subscribe("/plane_frame_cloud2", mo.on_plane_cloud)
         bus.subscribe("/frame_odom2", mo.on_odom)
     period_ns = int(round(1e9 / rate_hz))
+    metrics = []
     for fr in sio.NpzSequence(root, keys=keys, device=dev):
         t_ns = fr["index"] * period_ns
         stamp = (t_ns // 1_000_000_000, t_ns % 1_000_000_000)
         stamps.append(stamp)
+        if asf:
+            _, fm = pco.on_pair(fr["pos1"], fr["pos2"], stamp, fg1=fr.get("s_fg_mask"),
+                                fg2=fr.get("t_fg_mask"), gt_flow=fr.get("gt"))
+            if fm is not None:
+                metrics.append(fm)
+            continue
         pco.on_frame(fr["pos1"], fr.get("gt"), stamp,
                      gt_mask=fr.get("s_fg_mask") if src_mode == "gt" else None)
     res = dict(odom1=np.asarray(odom1, np.float64).reshape(-1, 7),
                odom2=np.asarray(odom2, np.float64).reshape(-1, 7), stamps=stamps,
                loops=mo.closer.constraints if mo else [])
+    if metrics:
+        res["flow_metrics"] = metrics
     if map_optimize:                                 # the last solve (None: no loop was closed)
         res["optimization"] = mo.closer.last_optimization if mo else None
         res["key_poses"] = [list(k) for k in mo.closer.key6d] if mo else []

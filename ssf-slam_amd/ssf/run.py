@@ -1,6 +1,7 @@
 """python -m ssf.run DATASET_PATH [--launch noSeg] [--tum traj.txt]: replay an npz scene-flow
 sequence through the device front-end as one of the reference's launch files wires its nodes
-(launch/run_onlyPC.launch, run_noSeg.launch, run_Seg.launch; ssf.nodes.LAUNCH_GRAPHS) and append
+(launch/run_onlyPC.launch, run_noSeg.launch, run_Seg.launch, run_noSeg_ActiveSceneFlow.launch,
+run_Seg_ActiveSceneFlow.launch with --weights; ssf.nodes.LAUNCH_GRAPHS) and append
 /frame_odom2 to a TUM trajectory (optionally with mapOptmization's loop closure, and with
 --map-cloud its accumulated map cloud saved as an npy file)."""
 from __future__ import annotations
@@ -32,6 +33,11 @@ def main(argv=None):
     ap.add_argument("--map-cloud", default=None, metavar="FILE.npy",
                     help="with --map-tum: keep the accumulated map cloud on the GPU, publish its 0.4 m "
                          "VoxelGrid on /sum_map_cloud_res3 and save the final one as float32 [M, 4]")
+    ap.add_argument("--weights", default=None, metavar="FILE",
+                    help="the ActiveSceneFlow launches: TFlow checkpoint (a state dict with the "
+                         "reference's keys, a DataParallel `module.` prefix accepted)")
+    ap.add_argument("--n-points", type=int, default=8192,
+                    help="the ActiveSceneFlow launches: points per cloud the network takes")
     ap.add_argument("--rate-hz", type=float, default=10.0,
                     help="frame rate of the synthetic stamps (frame k at k / rate)")
     a = ap.parse_args(argv)
@@ -45,6 +51,11 @@ def main(argv=None):
         ap.error("--map-cloud needs --map-tum")
     torch.cuda.set_device(a.device)
     kw = dict(map_cloud=True) if a.map_cloud else {}
+    from .nodes import ASF_LAUNCHES
+    if a.launch in ASF_LAUNCHES:
+        if a.weights is None:
+            ap.error(f"--launch {a.launch} needs --weights (no trained weights ship with the project)")
+        kw.update(weights=a.weights, n_points=a.n_points)
     res = run_sequence(a.dataset_path, a.tum, n_rows=a.rows, solver=a.solver, max_iter=a.iters,
                        seed=a.seed, launch=a.launch, map_tum_path=a.map_tum, map_optimize=a.map_optimize,
                        truncate_results=a.truncate, rate_hz=a.rate_hz, **kw)
@@ -59,6 +70,9 @@ def main(argv=None):
             np.save(f, res["map_cloud"])
         extra["map_cloud"] = {"file": a.map_cloud, "points": int(res["map_cloud"].shape[0]),
                               "keyframes": int(res["map_cloud_keyframes"])}
+    if res.get("flow_metrics"):                      # the dataset carries gt: the mean of each metric
+        fm = res["flow_metrics"]
+        extra["flow_metrics"] = {k: sum(m[k] for m in fm) / len(fm) for k in fm[0]}
     print(json.dumps({"launch": a.launch, "tum": a.tum, "tum_mode": "truncate" if a.truncate else "append",
                       "frames": len(res["stamps"]),
                       "odom1_poses": int(res["odom1"].shape[0]),
