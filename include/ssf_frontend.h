@@ -601,6 +601,48 @@ int32_t ssf_pose_graph_batch(ssf_ctx* ctx, void* stream, int32_t n_graphs, doubl
                              const double* d_prior_var, const ssf_pgo_params* params,
                              double* d_stats, double* d_cost_log);
 
+/* ssf_pose_graph_batch_robust is ssf_pose_graph_batch with an m-estimator on the loop edges (what
+ * wrapping the loop factor's noise model in gtsam::noiseModel::Robust does) and a per-edge report.
+ * With s = r^T r of an edge's whitened residual and e = sqrt(s) (GTSAM's convention):
+ *   kind             weight w(s)                 2 rho(s)                          default k
+ *   NONE             1                           s
+ *   HUBER            1 if e <= k, else k / e     s if e <= k, else 2 k (e - k / 2)  1.345
+ *   CAUCHY           k^2 / (k^2 + s)             k^2 log1p(s / k^2)                 0.1
+ *   GEMAN_MCCLURE    (k^2 / (k^2 + s))^2         k^2 s / (k^2 + s)                  1.0
+ * The loss applies to the loop edges (|i - j| != 1) only; chain edges and the prior stay
+ * quadratic, so the block-tridiagonal part is what it is without the loss.  IRLS Gauss-Newton:
+ * at every linearisation a loop edge's residual and Jacobians are scaled by sqrt(w); the cost
+ * (the stop rule, SSF_PGO_OUT_COST0, SSF_PGO_OUT_COST, d_cost_log) is 0.5 * the sum of s over
+ * the prior and the chain edges and of 2 rho(s) over the loop edges.  Steps are never rejected:
+ * a redescending loss (Cauchy, Geman-McClure) from a far start may raise the cost.
+ *   robust        nullable (NULL: kind NONE)
+ *   d_edge_out    nullable; SSF_PGO_EDGE_OUT_STRIDE doubles per edge at the call's edge offsets:
+ *                 the weight (1 for a chain edge) and the unweighted s, both from the evaluation
+ *                 whose cost is SSF_PGO_OUT_COST; NaN for every edge of a graph that ends with
+ *                 SSF_PGO_EMPTY, _BAD_INPUT, _TOO_MANY_LOOPS or _NOT_PD
+ * robust NULL or of kind NONE together with d_edge_out NULL is ssf_pose_graph_batch itself (the
+ * same kernels and launches).  SSF_E_ARG (before any HIP call) as ssf_pose_graph_batch, and on
+ * an unknown kind or, for a kind other than NONE, k not finite or <= 0. */
+typedef struct {
+    int32_t kind;           /* SSF_PGO_ROBUST_*                                         */
+    double k;               /* the loss's threshold / scale; unused for NONE            */
+} ssf_pgo_robust;
+enum {
+    SSF_PGO_ROBUST_NONE = 0, SSF_PGO_ROBUST_HUBER = 1, SSF_PGO_ROBUST_CAUCHY = 2,
+    SSF_PGO_ROBUST_GEMAN_MCCLURE = 3
+};
+#define SSF_PGO_EDGE_OUT_STRIDE 2
+enum { SSF_PGO_EDGE_WEIGHT = 0, SSF_PGO_EDGE_CHI2 = 1 };
+int32_t ssf_pgo_robust_default(int32_t kind, ssf_pgo_robust* out);   /* k = the table's default */
+int32_t ssf_pose_graph_batch_robust(ssf_ctx* ctx, void* stream, int32_t n_graphs, double* d_pose,
+                                    const int32_t* d_node_off, const int32_t* h_node_off,
+                                    const int32_t* d_edge_ij, const double* d_edge_meas,
+                                    const double* d_edge_var, const int32_t* d_edge_off,
+                                    const int32_t* h_edge_off, const double* d_prior_pose,
+                                    const double* d_prior_var, const ssf_pgo_params* params,
+                                    double* d_stats, double* d_cost_log,
+                                    const ssf_pgo_robust* robust, double* d_edge_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -1081,6 +1082,31 @@ int32_t ssf_pgo_params_default(ssf_pgo_params* out) {
     return SSF_OK;
 }
 
+int32_t ssf_pgo_robust_default(int32_t kind, ssf_pgo_robust* out) {
+    if (!out) return SSF_E_ARG;
+    double k;                       // GTSAM's defaults (noiseModel::mEstimator)
+    switch (kind) {
+        case SSF_PGO_ROBUST_NONE: k = 0.0; break;
+        case SSF_PGO_ROBUST_HUBER: k = 1.345; break;
+        case SSF_PGO_ROBUST_CAUCHY: k = 0.1; break;
+        case SSF_PGO_ROBUST_GEMAN_MCCLURE: k = 1.0; break;
+        default: return SSF_E_ARG;
+    }
+    out->kind = kind;
+    out->k = k;
+    return SSF_OK;
+}
+
+// both pose-graph entry points; robust: the loss kernels and the per-edge output
+static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
+                                const int32_t* d_node_off, const int32_t* h_node_off,
+                                const int32_t* d_edge_ij, const double* d_edge_meas,
+                                const double* d_edge_var, const int32_t* d_edge_off,
+                                const int32_t* h_edge_off, const double* d_prior_pose,
+                                const double* d_prior_var, const ssf_pgo_params* prm,
+                                double* d_stats, double* d_cost_log, bool robust, int rkind, double rk,
+                                double* d_edge_out);
+
 int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
                              const int32_t* d_node_off, const int32_t* h_node_off,
                              const int32_t* d_edge_ij, const double* d_edge_meas,
@@ -1088,6 +1114,41 @@ int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double*
                              const int32_t* h_edge_off, const double* d_prior_pose,
                              const double* d_prior_var, const ssf_pgo_params* prm,
                              double* d_stats, double* d_cost_log) {
+    return pose_graph_batch(c, stream, n_graphs, d_pose, d_node_off, h_node_off, d_edge_ij, d_edge_meas,
+                            d_edge_var, d_edge_off, h_edge_off, d_prior_pose, d_prior_var, prm, d_stats,
+                            d_cost_log, false, SSF_PGO_ROBUST_NONE, 0.0, nullptr);
+}
+
+int32_t ssf_pose_graph_batch_robust(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
+                                    const int32_t* d_node_off, const int32_t* h_node_off,
+                                    const int32_t* d_edge_ij, const double* d_edge_meas,
+                                    const double* d_edge_var, const int32_t* d_edge_off,
+                                    const int32_t* h_edge_off, const double* d_prior_pose,
+                                    const double* d_prior_var, const ssf_pgo_params* prm,
+                                    double* d_stats, double* d_cost_log, const ssf_pgo_robust* robust,
+                                    double* d_edge_out) {
+    if (!c) return SSF_E_ARG;
+    const int rkind = robust ? robust->kind : SSF_PGO_ROBUST_NONE;
+    if (rkind < SSF_PGO_ROBUST_NONE || rkind > SSF_PGO_ROBUST_GEMAN_MCCLURE)
+        return fail(c, SSF_E_ARG, "pose_graph_batch_robust: unknown loss kind");
+    if (rkind != SSF_PGO_ROBUST_NONE && !(std::isfinite(robust->k) && robust->k > 0.0))
+        return fail(c, SSF_E_ARG, "pose_graph_batch_robust: k must be finite and positive");
+    // no loss and no per-edge output: the plain kernels, launch for launch
+    const bool plain = rkind == SSF_PGO_ROBUST_NONE && !d_edge_out;
+    return pose_graph_batch(c, stream, n_graphs, d_pose, d_node_off, h_node_off, d_edge_ij, d_edge_meas,
+                            d_edge_var, d_edge_off, h_edge_off, d_prior_pose, d_prior_var, prm, d_stats,
+                            d_cost_log, !plain, rkind, rkind != SSF_PGO_ROBUST_NONE ? robust->k : 0.0,
+                            d_edge_out);
+}
+
+static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
+                                const int32_t* d_node_off, const int32_t* h_node_off,
+                                const int32_t* d_edge_ij, const double* d_edge_meas,
+                                const double* d_edge_var, const int32_t* d_edge_off,
+                                const int32_t* h_edge_off, const double* d_prior_pose,
+                                const double* d_prior_var, const ssf_pgo_params* prm,
+                                double* d_stats, double* d_cost_log, bool robust, int rkind, double rk,
+                                double* d_edge_out) {
     if (!c) return SSF_E_ARG;
     if (n_graphs < 0 || !prm || prm->max_iter < 0 || prm->max_iter > SSF_PGO_MAX_ITER ||
         !(prm->func_tol >= 0.0) ||
@@ -1120,10 +1181,17 @@ int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double*
     SSF_TRY_HIP(c, c->pgo_scratch.ensure(sizeof(double) * total), "alloc pose-graph scratch");
     SSF_TRY_HIP(c, hipMemcpyAsync(c->pgo_desc.p, c->pgo_h.data(), sizeof(ssf::PgoGraph) * (size_t)n_graphs,
                                   hipMemcpyHostToDevice, s), "H2D pose-graph descriptors");
-    hipError_t e = ssf::launch_pose_graph(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose, d_node_off,
-                                          d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
+    hipError_t e;
+    if (robust)
+        e = ssf::launch_pose_graph_robust(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose,
+                                          d_node_off, d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
                                           d_prior_var, prm->max_iter, prm->func_tol,
-                                          c->pgo_scratch.as<double>(), d_stats, d_cost_log);
+                                          c->pgo_scratch.as<double>(), d_stats, d_cost_log, rkind, rk, d_edge_out);
+    else
+        e = ssf::launch_pose_graph(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose, d_node_off,
+                                   d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
+                                   d_prior_var, prm->max_iter, prm->func_tol,
+                                   c->pgo_scratch.as<double>(), d_stats, d_cost_log);
     if (e != hipSuccess) return hip_fail(c, e, "pose_graph launch");
     return SSF_OK;
 }

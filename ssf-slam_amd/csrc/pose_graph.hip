@@ -32,6 +32,11 @@
 //                dense Cholesky with the rows strided over the threads, by panels of columns;
 //                dx = T^-1 (-g - A^T w): one more single-column substitution on lane 0
 //   The host picks the kernel (PgoGraph::wide, from K and E); the two share pgo_solve.
+//   k_pose_graph_robust / k_pose_graph_wide_robust are the same two solvers with an m-estimator on
+//   the loop edges (ssf_pgo_robust; IRLS, Triggs' first-order form): at every linearisation a loop
+//   edge's record is scaled by sqrt(w(s)), s its squared whitened residual, and it enters the cost
+//   with 2 rho(s).  Chain edges and the prior stay quadratic, so T is what it is without the loss.
+//   They also report every edge's weight and s (d_edge_out).
 //   No inter-work-group communication of any kind.  A graph writes its poses back only when it
 //   ends with SSF_PGO_OK / SSF_PGO_CONVERGED: it iterates on a copy in the context scratch.
 //   Every loop bound is a count the prologue validated (K, E from the host descriptor checked
@@ -151,6 +156,26 @@ SSF_DEV double pgo_block_max(double v, double* lds) {
     for (int i = 1; i < nw; ++i) m = fmax(m, lds[i]);
     __syncthreads();
     return m;
+}
+
+// The m-estimators of ssf_pgo_robust on the whitened error norm e = sqrt(s) (GTSAM's convention):
+// -> (the weight w(s), 2 rho(s)), by value: an out-parameter of a function that is not inlined
+// would live in scratch memory.  Out of line: the linearise phase is not the register peak.
+__device__ __noinline__ double2 pgo_robust_loss(int kind, double k, double s) {
+    double w = 1.0, r2 = s;
+    if (kind == SSF_PGO_ROBUST_HUBER) {
+        const double e = sqrt(s);
+        if (e > k) { w = k / e; r2 = 2.0 * k * (e - 0.5 * k); }
+    } else if (kind == SSF_PGO_ROBUST_CAUCHY) {
+        const double k2 = k * k;
+        w = k2 / (k2 + s);
+        r2 = k2 * log1p(s / k2);
+    } else if (kind == SSF_PGO_ROBUST_GEMAN_MCCLURE) {
+        const double k2 = k * k, c = k2 / (k2 + s);
+        w = c * c;
+        r2 = c * s;
+    }
+    return make_double2(w, r2);
 }
 
 // the right-hand side of one column of [ -g | A^T ] at node k: col 0 is -g, col 1 + 6 l + row is
@@ -277,13 +302,16 @@ SSF_DEV void pgo_substitute(const double* D, const double* O, int K, double* z, 
 // side on a lane of its own, the loop list and the capacitance vectors in LDS.  kWide = true: up
 // to SSF_PGO_MAX_LOOPS, the columns of A^T in passes of kPgoThreads, everything sized by L in the
 // graph's scratch.  A work-group whose graph belongs to the other kernel returns at once.
-template <bool kWide>
+// kRobust: the loss (rkind, rk) on the loop edges, and edge_out (nullable): two doubles per edge
+// (SSF_PGO_EDGE_*) at the host's edge offsets, NaN for a graph that fails.
+template <bool kWide, bool kRobust>
 SSF_DEV void pgo_solve(
     const PgoGraph* __restrict__ desc, double* __restrict__ pose, const int32_t* __restrict__ node_off,
     const int32_t* __restrict__ edge_ij, const double* __restrict__ edge_meas,
     const double* __restrict__ edge_var, const int32_t* __restrict__ edge_off,
     const double* __restrict__ prior_pose, const double* __restrict__ prior_var, int max_iter,
-    double func_tol, double* scratch, double* __restrict__ stats, double* __restrict__ cost_log) {
+    double func_tol, double* scratch, double* __restrict__ stats, double* __restrict__ cost_log,
+    int rkind = 0, double rk = 0.0, double* __restrict__ edge_out = nullptr) {
     __shared__ double red[kPgoThreads / 64];
     __shared__ double va[kWide ? 1 : kPgoMaxN], vb[kWide ? 1 : kPgoMaxN];
     __shared__ int2 ij_s[kPgoTile];
@@ -301,6 +329,8 @@ SSF_DEV void pgo_solve(
     double* st = stats + (size_t)g * SSF_PGO_OUT_STRIDE;
     double* clog = cost_log ? cost_log + (size_t)g * (size_t)(max_iter + 1) : nullptr;
     const double kNaN = __builtin_nan("");
+    // the host validated its edge offsets against each other: the call's output has E rows from edge0
+    double* EO = kRobust && edge_out ? edge_out + (size_t)SSF_PGO_EDGE_OUT_STRIDE * (size_t)G.edge0 : nullptr;
 
     // ---- prologue: validation before any indexed access
     if (tid == 0) { bad_s = 0; nloop_s = 0; fail_s = 0; }
@@ -373,6 +403,9 @@ SSF_DEV void pgo_solve(
             st[SSF_PGO_OUT_DX] = 0.0; st[SSF_PGO_OUT_LOOPS] = status == SSF_PGO_EMPTY || status == SSF_PGO_BAD_INPUT ? 0.0 : (double)nloop_s;
             st[6] = 0.0; st[7] = 0.0;
         }
+        if constexpr (kRobust)
+            if (EO)
+                for (int e = tid; e < SSF_PGO_EDGE_OUT_STRIDE * E; e += kPgoThreads) EO[e] = kNaN;
         return;
     }
 
@@ -414,7 +447,28 @@ SSF_DEV void pgo_solve(
             }
             double s = 0.0;
             for (int c = 0; c < 6; ++c) s += rec[c] * rec[c];
-            cs[0] += s;
+            if constexpr (kRobust) {
+                // a loop edge: weight and 2 rho from s, its record scaled in place (what the
+                // assemble phase, PgoColumn and the capacitance read)
+                double w = 1.0, rho2 = s;
+                if (e < E) {
+                    const int i = IJ[2 * e], j = IJ[2 * e + 1];
+                    if (i - j != 1 && j - i != 1) {
+                        const double2 wr = pgo_robust_loss(rkind, rk, s);
+                        w = wr.x;
+                        rho2 = wr.y;
+                        const double sw = sqrt(w);
+                        for (int c = 0; c < kPgoRec; ++c) rec[c] *= sw;
+                    }
+                    if (EO) {
+                        EO[SSF_PGO_EDGE_OUT_STRIDE * (size_t)e + SSF_PGO_EDGE_WEIGHT] = w;
+                        EO[SSF_PGO_EDGE_OUT_STRIDE * (size_t)e + SSF_PGO_EDGE_CHI2] = s;
+                    }
+                }
+                cs[0] += rho2;
+            } else {
+                cs[0] += s;
+            }
         }
         block_sum<1>(cs, red);                     // its barriers also publish REC
         cost = 0.5 * cs[0];
@@ -782,6 +836,9 @@ SSF_DEV void pgo_solve(
     if (status == SSF_PGO_OK || status == SSF_PGO_CONVERGED)
         for (int k = tid; k < K; k += kPgoThreads)
             for (int c = 0; c < 7; ++c) P[7 * (size_t)k + c] = X[7 * (size_t)k + c];
+    if constexpr (kRobust)
+        if (EO && status == SSF_PGO_NOT_PD)
+            for (int e = tid; e < SSF_PGO_EDGE_OUT_STRIDE * E; e += kPgoThreads) EO[e] = kNaN;
     if (tid == 0) {
         const bool ok = status != SSF_PGO_NOT_PD;
         st[SSF_PGO_OUT_STATUS] = status; st[SSF_PGO_OUT_ITERATIONS] = ok ? iters : 0.0;
@@ -799,13 +856,25 @@ SSF_DEV void pgo_solve(
         double func_tol, double *scratch, double *__restrict__ stats, double *__restrict__ cost_log
 
 __global__ __launch_bounds__(kPgoThreads) void k_pose_graph(SSF_PGO_KERNEL_ARGS) {
-    pgo_solve<false>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
-                     max_iter, func_tol, scratch, stats, cost_log);
+    pgo_solve<false, false>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
+                            max_iter, func_tol, scratch, stats, cost_log);
 }
 
 __global__ __launch_bounds__(kPgoThreads) void k_pose_graph_wide(SSF_PGO_KERNEL_ARGS) {
-    pgo_solve<true>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
-                    max_iter, func_tol, scratch, stats, cost_log);
+    pgo_solve<true, false>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
+                           max_iter, func_tol, scratch, stats, cost_log);
+}
+
+__global__ __launch_bounds__(kPgoThreads) void k_pose_graph_robust(SSF_PGO_KERNEL_ARGS, int rkind, double rk,
+                                                                   double* __restrict__ edge_out) {
+    pgo_solve<false, true>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
+                           max_iter, func_tol, scratch, stats, cost_log, rkind, rk, edge_out);
+}
+
+__global__ __launch_bounds__(kPgoThreads) void k_pose_graph_wide_robust(SSF_PGO_KERNEL_ARGS, int rkind, double rk,
+                                                                        double* __restrict__ edge_out) {
+    pgo_solve<true, true>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
+                          max_iter, func_tol, scratch, stats, cost_log, rkind, rk, edge_out);
 }
 
 // Both kernels run over every graph of the batch; a work-group returns at once when its graph
@@ -827,6 +896,29 @@ hipError_t launch_pose_graph(hipStream_t s, int n_graphs, bool any_narrow, bool 
         hipLaunchKernelGGL(k_pose_graph_wide, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose, node_off,
                            edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter, func_tol,
                            scratch, stats, cost_log);
+    }
+    return hipGetLastError();
+}
+
+// The same dispatch onto the kernels with a loss on the loop edges and the per-edge output.
+hipError_t launch_pose_graph_robust(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
+                                    const PgoGraph* desc, double* pose, const int32_t* node_off,
+                                    const int32_t* edge_ij, const double* edge_meas, const double* edge_var,
+                                    const int32_t* edge_off, const double* prior_pose, const double* prior_var,
+                                    int max_iter, double func_tol, double* scratch, double* stats,
+                                    double* cost_log, int rkind, double rk, double* edge_out) {
+    if (n_graphs <= 0) return hipSuccess;
+    if (any_narrow) {
+        kmark(s, "k_pose_graph_robust");
+        hipLaunchKernelGGL(k_pose_graph_robust, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose, node_off,
+                           edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter, func_tol,
+                           scratch, stats, cost_log, rkind, rk, edge_out);
+    }
+    if (any_wide) {
+        kmark(s, "k_pose_graph_wide_robust");
+        hipLaunchKernelGGL(k_pose_graph_wide_robust, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose,
+                           node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter,
+                           func_tol, scratch, stats, cost_log, rkind, rk, edge_out);
     }
     return hipGetLastError();
 }

@@ -319,5 +319,12 @@ hipError_t launch_pose_graph(hipStream_t s, int n_graphs, bool any_narrow, bool 
                              const double* edge_var, const int32_t* edge_off, const double* prior_pose,
                              const double* prior_var, int max_iter, double func_tol, double* scratch,
                              double* stats, double* cost_log);
+// the kernels with a loss (ssf_pgo_robust: rkind, rk) on the loop edges; edge_out is nullable
+hipError_t launch_pose_graph_robust(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
+                                    const PgoGraph* desc, double* pose, const int32_t* node_off,
+                                    const int32_t* edge_ij, const double* edge_meas, const double* edge_var,
+                                    const int32_t* edge_off, const double* prior_pose, const double* prior_var,
+                                    int max_iter, double func_tol, double* scratch, double* stats,
+                                    double* cost_log, int rkind, double rk, double* edge_out);
 
 }  // namespace ssf

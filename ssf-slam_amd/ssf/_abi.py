@@ -41,6 +41,7 @@ EXPORTS = [
     "ssf_edge_table_batch", "ssf_register_batch_edges", "ssf_kabsch_f32_batch",
     "ssf_set_mask_schedule", "ssf_register_plan", "ssf_pgo_params_default", "ssf_pose_graph_batch",
     "ssf_transform_clouds_batch", "ssf_subsample_batch",
+    "ssf_pgo_robust_default", "ssf_pose_graph_batch_robust",
 ]
 # ssf_subsample_batch: limits and per-frame status codes
 SAMPLE_MAX_NB, SAMPLE_MAX_POINTS = 8192, 1 << 24
@@ -68,8 +69,19 @@ PGO_OK, PGO_CONVERGED, PGO_EMPTY, PGO_BAD_INPUT, PGO_TOO_MANY_LOOPS, PGO_NOT_PD 
 PGO_STATUS = {0: "ok", 1: "converged", 2: "empty", 3: "bad_input", 4: "too_many_loops", 5: "not_pd"}
 
 
+# ssf_pgo_robust: the loss on the loop edges (ssf_pose_graph_batch_robust) and its per-edge output
+PGO_ROBUST_NONE, PGO_ROBUST_HUBER, PGO_ROBUST_CAUCHY, PGO_ROBUST_GEMAN_MCCLURE = range(4)
+PGO_ROBUST_KINDS = dict(none=0, huber=1, cauchy=2, geman_mcclure=3)
+PGO_EDGE_OUT_STRIDE = 2
+PGO_EDGE_OUT = dict(WEIGHT=0, CHI2=1)
+
+
 class PgoParams(C.Structure):
     _fields_ = [("max_iter", C.c_int32), ("func_tol", C.c_double)]
+
+
+class PgoRobust(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("k", C.c_double)]
 
 
 class IcpParams(C.Structure):
@@ -202,6 +214,11 @@ def lib():
     L.ssf_pgo_params_default.restype = i32
     L.ssf_pose_graph_batch.argtypes = [vp, vp, i32] + [vp] * 10 + [C.POINTER(PgoParams), vp, vp]
     L.ssf_pose_graph_batch.restype = i32
+    L.ssf_pgo_robust_default.argtypes = [i32, C.POINTER(PgoRobust)]
+    L.ssf_pgo_robust_default.restype = i32
+    L.ssf_pose_graph_batch_robust.argtypes = [vp, vp, i32] + [vp] * 10 + [C.POINTER(PgoParams), vp, vp,
+                                                                          C.POINTER(PgoRobust), vp]
+    L.ssf_pose_graph_batch_robust.restype = i32
     L.ssf_pn2_last_error.argtypes = []
     L.ssf_pn2_last_error.restype = C.c_char_p
     L.ssf_pn2_furthest_point_sample.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]

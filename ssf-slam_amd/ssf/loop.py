@@ -11,8 +11,9 @@ noise = the ICP fitness score).  By default the published pose is the loop-adjus
 ``LoopCloser(optimize=True)`` also records the factors of addOdomFactor (:147-165), optimises
 the pose graph on the GPU at every loop closure (``optimize_pose_graphs`` <- runOptimize
 :280-293, batched Gauss-Newton in pose_graph.hip, not GTSAM's iSAM2) and rewrites every
-keyframe pose (correctPoses :296-332), see DESIGN.md §6.7.  ``LoopCloser(map_cloud=True)`` also
-keeps the accumulated map cloud (mapCloudPtr: updateKeyPose :309-311, the rebuild of
+keyframe pose (correctPoses :296-332); ``robust=pgo_robust("huber")`` puts
+a robust loss on the loop edges of those solves.  ``LoopCloser(map_cloud=True)`` also keeps the
+accumulated map cloud (mapCloudPtr: updateKeyPose :309-311, the rebuild of
 correctPoses :320-325) on the device in an ``ssf.MapCloud``; a new keyframe
 goes into the map at its stored key pose (the reference places it at its iSAM2 estimate).
 
@@ -134,16 +135,48 @@ def pgo_params(max_iter=8, func_tol=1e-6):
     return p
 
 
-def optimize_pose_graphs(fe: Frontend, graphs, params=None):
+def pgo_robust(kind, k=None):
+    """The loss on the loop edges of a pose graph (ssf_pgo_robust; what GTSAM's
+    noiseModel::Robust does to a loop factor): kind "none", "huber", "cauchy" or "geman_mcclure",
+    k its threshold (default: GTSAM's, 1.345 / 0.1 / 1.0)."""
+    if not isinstance(kind, str) or kind not in _abi.PGO_ROBUST_KINDS:
+        raise ValueError(f"pgo_robust: kind is one of {', '.join(_abi.PGO_ROBUST_KINDS)}, not {kind!r}")
+    r = _abi.PgoRobust()
+    if _abi.lib().ssf_pgo_robust_default(_abi.PGO_ROBUST_KINDS[kind], C.byref(r)) != _abi.SSF_OK:
+        raise ValueError(f"pgo_robust: kind {kind!r} rejected")
+    if k is not None:
+        try:
+            k = float(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"pgo_robust: k must be a number, not {k!r}") from None
+        if kind != "none" and not (math.isfinite(k) and k > 0.0):
+            raise ValueError(f"pgo_robust: k must be finite and positive, not {k!r}")
+        r.k = k
+    return r
+
+
+def parse_robust(text):
+    """"KIND[:K]" (the --map-robust / --robust command-line form) -> pgo_robust(KIND, K)."""
+    kind, sep, k = str(text).partition(":")
+    if sep and not k:
+        raise ValueError(f"robust loss {text!r}: nothing after the colon")
+    return pgo_robust(kind, k if sep else None)
+
+
+def optimize_pose_graphs(fe: Frontend, graphs, params=None, robust=None, edge_out=False):
     """Batched pose-graph optimisation, one launch for every graph of the list.  A graph is a
     dict(poses [K, 7] f64 (q xyzw, t), edge_ij [E, 2] graph-local, edge_meas [E, 7], edge_var
     [E, 6] (rotation then translation), prior_pose [7], prior_var [6] on node 0).
     -> list of dict(poses [K, 7], status (PGO_*), status_name, iterations, cost0, cost, dx, loops,
-    cost_log).  A graph whose status is not ok / converged gets its poses back unchanged."""
+    cost_log).  A graph whose status is not ok / converged gets its poses back unchanged.
+    robust (pgo_robust): a loss on the loop edges (|i - j| != 1); with it or with edge_out every
+    result also carries edge_weight [E] and edge_chi2 [E] (the unweighted squared whitened
+    residual) of the evaluation `cost` belongs to, NaN for a graph that failed."""
     G = len(graphs)
     if G == 0:
         return []
     params = params or pgo_params()
+    with_edges = robust is not None or bool(edge_out)
     f64 = lambda key, w: [np.ascontiguousarray(g[key], np.float64).reshape(-1, w) for g in graphs]  # noqa: E731
     poses, meas, var = f64("poses", 7), f64("edge_meas", 7), f64("edge_var", 6)
     ij = [np.ascontiguousarray(g["edge_ij"], np.int32).reshape(-1, 2) for g in graphs]
@@ -168,10 +201,16 @@ def optimize_pose_graphs(fe: Frontend, graphs, params=None):
     d_noff, d_eoff = h_noff.to(dev), h_eoff.to(dev)
     stats = torch.zeros(G, _abi.PGO_OUT_STRIDE, dtype=torch.float64, device=dev)
     clog = torch.zeros(G, params.max_iter + 1, dtype=torch.float64, device=dev)
-    fe._check(_abi.lib().ssf_pose_graph_batch(
-        fe._h, _stream(dev), G, _ptr(d_pose), _ptr(d_noff), C.c_void_p(h_noff.data_ptr()), _ptr(d_ij),
-        _ptr(d_meas), _ptr(d_var), _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(d_prior), _ptr(d_pvar),
-        C.byref(params), _ptr(stats), _ptr(clog)), "ssf_pose_graph_batch")
+    args = (fe._h, _stream(dev), G, _ptr(d_pose), _ptr(d_noff), C.c_void_p(h_noff.data_ptr()), _ptr(d_ij),
+            _ptr(d_meas), _ptr(d_var), _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(d_prior), _ptr(d_pvar),
+            C.byref(params), _ptr(stats), _ptr(clog))
+    if with_edges:
+        eout = torch.zeros(int(h_eoff[-1]) + 1, _abi.PGO_EDGE_OUT_STRIDE, dtype=torch.float64, device=dev)
+        fe._check(_abi.lib().ssf_pose_graph_batch_robust(*args, None if robust is None else C.byref(robust),
+                                                         _ptr(eout)), "ssf_pose_graph_batch_robust")
+        eo = eout.cpu().numpy()
+    else:
+        fe._check(_abi.lib().ssf_pose_graph_batch(*args), "ssf_pose_graph_batch")
     out_pose, st, cl = d_pose.cpu().numpy(), stats.cpu().numpy(), clog.cpu().numpy()
     res = []
     for k in range(G):
@@ -183,6 +222,10 @@ def optimize_pose_graphs(fe: Frontend, graphs, params=None):
                         cost=float(o[_abi.PGO_OUT["COST"]]), dx=float(o[_abi.PGO_OUT["DX"]]),
                         loops=int(o[_abi.PGO_OUT["LOOPS"]]),
                         cost_log=[float(v) for v in cl[k] if not math.isnan(v)]))
+        if with_edges:
+            rows = eo[int(h_eoff[k]):int(h_eoff[k + 1])]
+            res[-1].update(edge_weight=rows[:, _abi.PGO_EDGE_OUT["WEIGHT"]].copy(),
+                           edge_chi2=rows[:, _abi.PGO_EDGE_OUT["CHI2"]].copy())
     return res
 
 
@@ -248,6 +291,10 @@ class LoopCloser:
     graph_edges: list = field(default_factory=list)    # (i, j, measurement 7 doubles, 6 variances)
     graph_prior: np.ndarray | None = None
     last_optimization: dict | None = None
+    # a loss on the loop edges of every solve (pgo_robust); the solves then also report the
+    # weight of every edge (loop_weights).  Nothing is rejected: a down-weighted loop stays in
+    # the graph and its correction stays in trans_loop_adjust
+    robust: object | None = None
     # map_cloud=True: the keyframe clouds live in a device store and the accumulated map
     # (mapCloudPtr, updateKeyPose :309-311) is kept equal to every keyframe under its current key
     # pose: appended per keyframe, rebuilt in one launch when the poses are rewritten
@@ -405,14 +452,26 @@ class LoopCloser:
     def close_loop(self, c: LoopConstraint):
         """runOptimize + correctPoses for one closed loop -> the corrected T_map_0_curr."""
         self.add_loop_edge(c)
-        return self.apply_optimization(optimize_pose_graphs(self.fe, [self.pose_graph()])[0])
+        kw = {} if self.robust is None else dict(robust=self.robust, edge_out=True)
+        return self.apply_optimization(optimize_pose_graphs(self.fe, [self.pose_graph()], **kw)[0])
+
+    def loop_weights(self):
+        """[(key_cur, key_pre, weight)] of the loop edges in the last solve, in graph order (a
+        solve with `robust`; [] before the first one)."""
+        res = self.last_optimization
+        if res is None or "edge_weight" not in res:
+            return []
+        return [(int(e[0]), int(e[1]), float(w)) for e, w in zip(self.graph_edges, res["edge_weight"])
+                if abs(int(e[0]) - int(e[1])) != 1]
 
 
-def optimize_loop_closers(fe: Frontend, closers, constraints, params=None):
+def optimize_loop_closers(fe: Frontend, closers, constraints, params=None, robust=None):
     """Several sequences that closed a loop in the same step, solved in one launch: adds each
     constraint to its closer's graph, optimises all graphs together and applies correctPoses to
-    each.  -> the corrected T_map_0_curr of every closer."""
+    each.  -> the corrected T_map_0_curr of every closer.  robust (pgo_robust): the loss on the
+    loop edges of every graph of the launch; the closers then hold the edge weights."""
     for lc, c in zip(closers, constraints):
         lc.add_loop_edge(c)
-    res = optimize_pose_graphs(fe, [lc.pose_graph() for lc in closers], params)
+    kw = {} if robust is None else dict(robust=robust, edge_out=True)
+    res = optimize_pose_graphs(fe, [lc.pose_graph() for lc in closers], params, **kw)
     return [lc.apply_optimization(r) for lc, r in zip(closers, res)]

@@ -30,6 +30,10 @@ def main(argv=None):
     ap.add_argument("--map-optimize", action="store_true",
                     help="with --map-tum: optimise the pose graph on a loop closure and rewrite the "
                          "keyframe poses (runOptimize / correctPoses)")
+    ap.add_argument("--map-robust", default=None, metavar="KIND[:K]",
+                    help="with --map-optimize: a robust loss on the loop edges of the pose graph, "
+                         "huber, cauchy or geman_mcclure (or none), K its threshold (default 1.345 / "
+                         "0.1 / 1.0)")
     ap.add_argument("--map-cloud", default=None, metavar="FILE.npy",
                     help="with --map-tum: keep the accumulated map cloud on the GPU, publish its 0.4 m "
                          "VoxelGrid on /sum_map_cloud_res3 and save the final one as float32 [M, 4]")
@@ -49,8 +53,16 @@ def main(argv=None):
               f"--truncate starts a new file", file=sys.stderr)
     if a.map_cloud and a.map_tum is None:
         ap.error("--map-cloud needs --map-tum")
-    torch.cuda.set_device(a.device)
     kw = dict(map_cloud=True) if a.map_cloud else {}
+    if a.map_robust is not None:
+        if not a.map_optimize:
+            ap.error("--map-robust needs --map-optimize")
+        from .loop import parse_robust
+        try:
+            kw["map_robust"] = parse_robust(a.map_robust)
+        except ValueError as e:
+            ap.error(f"--map-robust: {e}")
+    torch.cuda.set_device(a.device)
     from .nodes import ASF_LAUNCHES
     if a.launch in ASF_LAUNCHES:
         if a.weights is None:
@@ -64,6 +76,8 @@ def main(argv=None):
         opt = res["optimization"]
         extra = {"map_optimize": None if opt is None else
                  {k: opt[k] for k in ("status_name", "iterations", "cost0", "cost", "loops")}}
+        if a.map_robust is not None and opt is not None:
+            extra["map_optimize"]["robust"] = a.map_robust
     if a.map_cloud:
         import numpy as np
         with open(a.map_cloud, "wb") as f:           # the name as given (np.save appends .npy to a path)

@@ -7,7 +7,12 @@ the L = 32 line of the same G and K (`--only` picks lines by name).
 
 HIP events around the ABI call on the current stream, one synchronise per sample, warm-up
 first, median of --runs samples (>= 20).  Every sample starts from the same drifted poses (a
-device-to-device copy outside the timed region).  Writes profiles/pgo_bench.json."""
+device-to-device copy outside the timed region).  Writes profiles/pgo_bench.json.
+
+--robust KIND[:K] times ssf_pose_graph_batch_robust with that loss on the loop edges (and the
+per-edge output) against the plain call instead: the `batch` and `long` lines, plain and robust
+alternated in one process, three runs of each (every run: warm-up, then the median of --runs
+samples).  Writes profiles/pgo_robust_bench.json."""
 import argparse
 import ctypes as C
 import json
@@ -65,7 +70,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "pgo_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/pgo_bench.json (pgo_robust_bench.json with --robust)")
+    ap.add_argument("--robust", default=None, metavar="KIND[:K]",
+                    help="time this loss (huber, cauchy, geman_mcclure; K default 1.345 / 0.1 / 1.0) against the plain call")
     ap.add_argument("--only", default="", help="comma-separated line names (default: all)")
     a = ap.parse_args()
     only = [n for n in a.only.split(",") if n]
@@ -73,15 +80,26 @@ def main():
         ap.error(f"--only: unknown line in {only}")
     if a.runs < 20:
         ap.error("--runs must be at least 20")
+    if a.robust and only:
+        ap.error("--robust times the batch and long lines: no --only")
     import torch
     from ssf import Frontend, _abi
+    robust = None
+    if a.robust:
+        from ssf.loop import parse_robust
+        try:
+            robust = parse_robust(a.robust)
+        except ValueError as e:
+            ap.error(f"--robust: {e}")
+        only = ["batch", "long"]
+    a.out = a.out or os.path.join(REPO, "profiles", "pgo_robust_bench.json" if robust else "pgo_bench.json")
     from ssf.frontend import _ptr, _stream
     dev = torch.device("cuda", 0)
     fe = Frontend(64, device=dev)
     L = _abi.lib()
     prm = _abi.PgoParams()
     L.ssf_pgo_params_default(C.byref(prm))
-    results = []
+    results, summary = [], []
     for sh in [sh for sh in SHAPES if not only or sh["name"] in only]:
         G, K, nl = sh["G"], sh["K"], sh["L"]
         gs = [circle(K, nl, 100 + (g % 8)) for g in range(min(G, 8))]
@@ -96,40 +114,61 @@ def main():
         d_noff, d_eoff = h_noff.to(dev), h_eoff.to(dev)
         pose = pose0.clone()
         stats = torch.zeros(G, _abi.PGO_OUT_STRIDE, dtype=torch.float64, device=dev)
+        eout = torch.zeros(G * (K - 1 + nl), _abi.PGO_EDGE_OUT_STRIDE, dtype=torch.float64, device=dev)
 
-        def call():
-            rc = L.ssf_pose_graph_batch(fe._h, _stream(dev), G, _ptr(pose), _ptr(d_noff),
-                                        C.c_void_p(h_noff.data_ptr()), _ptr(ij), _ptr(meas), _ptr(var),
-                                        _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(prior), _ptr(pvar),
-                                        C.byref(prm), _ptr(stats), None)
-            fe._check(rc, "ssf_pose_graph_batch")
+        def call(rb):
+            args = (fe._h, _stream(dev), G, _ptr(pose), _ptr(d_noff), C.c_void_p(h_noff.data_ptr()), _ptr(ij),
+                    _ptr(meas), _ptr(var), _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(prior), _ptr(pvar),
+                    C.byref(prm), _ptr(stats), None)
+            if rb is None:
+                fe._check(L.ssf_pose_graph_batch(*args), "ssf_pose_graph_batch")
+            else:
+                fe._check(L.ssf_pose_graph_batch_robust(*args, C.byref(rb), _ptr(eout)), "ssf_pose_graph_batch_robust")
 
-        ms = []
-        for k in range(a.warmup + a.runs):
-            pose.copy_(pose0)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call()
-            e1.record()
-            e1.synchronize()
-            if k >= a.warmup:
-                ms.append(e0.elapsed_time(e1))
-        st = stats.cpu().numpy()
-        status = sorted(set(int(v) for v in st[:, 0]))
-        row = dict(sh, runs=a.runs, warmup=a.warmup, median_ms=float(np.median(ms)), min_ms=float(np.min(ms)),
-                   max_ms=float(np.max(ms)), iterations=sorted(set(int(v) for v in st[:, 1])),
-                   status=[_abi.PGO_STATUS[s] for s in status], cost0=float(st[0, 2]), cost=float(st[0, 3]),
-                   max_iter=prm.max_iter, func_tol=prm.func_tol)
+        def sample(rb):
+            ms = []
+            for k in range(a.warmup + a.runs):
+                pose.copy_(pose0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                call(rb)
+                e1.record()
+                e1.synchronize()
+                if k >= a.warmup:
+                    ms.append(e0.elapsed_time(e1))
+            st = stats.cpu().numpy()
+            status = sorted(set(int(v) for v in st[:, 0]))
+            row = dict(sh, runs=a.runs, warmup=a.warmup, median_ms=float(np.median(ms)), min_ms=float(np.min(ms)),
+                       max_ms=float(np.max(ms)), iterations=sorted(set(int(v) for v in st[:, 1])),
+                       status=[_abi.PGO_STATUS[s] for s in status], cost0=float(st[0, 2]), cost=float(st[0, 3]),
+                       max_iter=prm.max_iter, func_tol=prm.func_tol)
+            if any(s not in (_abi.PGO_OK, _abi.PGO_CONVERGED) for s in status):
+                raise SystemExit(f"{sh['name']}: a graph failed: {row['status']}")
+            return row
+
+        if robust is not None:                       # plain and robust in turn, three runs of each
+            for rep in range(3):
+                for label, rb in (("plain", None), (a.robust, robust)):
+                    row = dict(sample(rb), loss=label, rep=rep)
+                    print(json.dumps(row), flush=True)
+                    results.append(row)
+            med = lambda label: [r["median_ms"] for r in results if r["name"] == sh["name"] and r["loss"] == label]  # noqa: E731
+            summary.append(dict(name=sh["name"], plain_median_ms=med("plain"), robust_median_ms=med(a.robust),
+                                plain_spread=max(med("plain")) / min(med("plain")) - 1.0,
+                                robust_over_plain=float(np.median(med(a.robust)) / np.median(med("plain")))))
+            print(json.dumps(summary[-1]), flush=True)
+            continue
+        row = sample(None)
         ref = [r for r in results if r["name"] == sh.get("ref")]
         if ref:                                      # against the L = 32 line of the same G and K
             row["ratio_to_l32"] = row["median_ms"] / ref[0]["median_ms"]
         print(json.dumps(row), flush=True)
-        if any(s not in (_abi.PGO_OK, _abi.PGO_CONVERGED) for s in status):
-            raise SystemExit(f"{sh['name']}: a graph failed: {row['status']}")
         results.append(row)
     out = dict(tool="tools/bench_pgo.py", device=torch.cuda.get_device_properties(0).name,
                arch=torch.cuda.get_device_properties(0).gcnArchName, timing="HIP events, one sync per sample",
                shapes=results)
+    if robust is not None:
+        out.update(robust=a.robust, k=robust.k, protocol="plain and robust alternated, three runs of each", summary=summary)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
