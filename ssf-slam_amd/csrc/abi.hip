@@ -793,7 +793,7 @@ static int32_t mask_pose_batch(ssf_ctx* c, void* stream, int32_t n_frames, const
     const int64_t total = h_frame_off[n_frames];
     for (int f = 0; f < n_frames; ++f) {
         if (h_frame_off[f + 1] < h_frame_off[f]) return fail(c, SSF_E_ARG, "mask_pose_batch: offsets not monotone");
-        // the streaming loops address a frame with 32-bit byte offsets (mask_pose.hip load3_off)
+        // the streaming loops address a frame with 32-bit byte offsets (mask_common.hpp load3_off)
         if (h_frame_off[f + 1] - h_frame_off[f] > (int64_t)(0xFFFFFFFFu / (3 * sizeof(T))))
             return fail(c, SSF_E_ARG, "mask_pose_batch: a frame above 2^32 / (3 sizeof(T)) points");
     }
@@ -808,7 +808,7 @@ static int32_t mask_pose_batch(ssf_ctx* c, void* stream, int32_t n_frames, const
     } else {
         SSF_TRY_HIP(c, hipEventSynchronize(ds.copied), "draws event");   // staging reusable
     }
-    const size_t rec_need = mode == SSF_MASK_GMM ? sizeof(uint2) * (size_t)(total + 2 * (int64_t)n_frames + 2) + sizeof(uint32_t) * (size_t)(total + 64 * (int64_t)n_frames) : 0;
+    const size_t rec_need = mode == SSF_MASK_GMM ? ssf::mask_rec_bytes(total, n_frames) : 0;
     // parts per frame: fixed, or automatic -- enough to fill the resident work-group slots
     if (c->mask_slots < 0) c->mask_slots = ssf::mask_pose_slots(c->device);
     int G = c->mask_split;

@@ -275,6 +275,15 @@ hipError_t launch_subsample(hipStream_t s, int n_frames, const float* pts, int s
                             int32_t* idx, float* xyz, int32_t* n_out, int32_t* status);
 size_t mask_sync_bytes(int n_frames);
 size_t mask_parts_bytes(int n_frames, int G);
+// The Lloyd record / queue buffer of a launch of `total` points in n_frames frames: 8-byte
+// records, one per point, kLloydSpareRecs spare per frame (its even start and the spare slot
+// after it) and a pair at the end; then 4-byte relabel-queue entries, one per point and
+// kLloydSpareQueue spare slots per frame.  The kernel's side: mask_lloyd.hpp.
+constexpr int kLloydSpareRecs = 2;
+constexpr int kLloydSpareQueue = 64;
+constexpr int64_t lloyd_rec_count(int64_t total, int n_frames) { return total + kLloydSpareRecs * (int64_t)n_frames + 2; }
+constexpr int64_t lloyd_queue_count(int64_t total, int n_frames) { return total + kLloydSpareQueue * (int64_t)n_frames; }
+size_t mask_rec_bytes(int64_t total, int n_frames);
 
 // ---- launchers (loop.hip) ----
 struct IcpState {             // one per ICP problem, device-resident across iterations

@@ -6,6 +6,7 @@ Bars: labels identical to sklearn's on the fixtures (>= 99.9 % required, BASELIN
 centre indices and KMeans / EM iteration counts identical, R/t within 1e-5 m / 1e-6 rad
 (observed ~1e-12), published [t, q] likewise.
 """
+import functools
 import glob
 import os
 
@@ -211,6 +212,66 @@ def test_frame_split_work_groups_take_several_tickets(oracle, dev):
     for k in (0, n_fr - 1):
         r = oracle.mask_and_pose(fr[k][0], fr[k][1], draws[k])
         assert int(o[k, 19]) == int(r["info"]["kmeans_iter"]) and int(o[k, 20]) == int(r["info"]["em_iter"])
+
+
+KPP_BIG_DRAWS = np.random.default_rng(21).random(3)
+
+
+@functools.lru_cache(maxsize=None)
+def _kpp_big_frame():
+    p, f, _ = frame(9, 3, n_rows=64, n_az=4100)
+    assert p.shape[0] == 64 * 4100
+    return p, f
+
+
+@functools.lru_cache(maxsize=None)
+def _kpp_big_reference():
+    from oracle import oracle as O
+    p, f = _kpp_big_frame()
+    return O.mask_and_pose(p, f, KPP_BIG_DRAWS)
+
+
+@functools.lru_cache(maxsize=None)
+def _kpp_big_device(G):
+    import ssf
+    p, f = _kpp_big_frame()
+    dev = torch.device("cuda", 0)
+    fe = ssf.Frontend(64, device=0)
+    fe.mask_split(G)
+    out, bg, _ = _run(fe, dev, [p], [f], draws=KPP_BIG_DRAWS[None, :])
+    return out[0], bg
+
+
+@pytest.mark.parametrize("G", [1, 2])
+def test_kmeanspp_part_above_block_totals_vs_oracle(oracle, dev, G):
+    """k-means++ when a part's 64-point block totals do not fit the kernel's LDS array
+    (kKppBlocks = 4096): one frame of 64 x 4100 = 262 400 points.  With the split fixed at 1 a
+    wave's segment is 342 blocks, 342 x 12 waves = 4104 > 4096, so the draws are found by the
+    sequential scan of the segment; at 2 the parts hold 131 200 points (2052 block totals) and take
+    the block-total path.  Both must pick the oracle's indices and run its iteration counts; bars
+    as in test_gpu_mask_em.py.
+
+    Seed policy: the frame (sequence 9, scan 3) and default_rng(21) were admitted on the oracle
+    alone, the first pair tried.  EM: the oracle's |lb - prev| per iteration is inf, 4.24, 9.4e-2,
+    1.179e-3, 3.9e-4; its closest approach to the 1e-3 threshold is 1.8e-4, against rounding
+    differences of about 1e-9, so the count is not knife-edge.  k-means++: draw 1 falls 1.5e-5 of
+    the potential above the cumulative sum at the index before the chosen one (127 054) and 5.1e-6
+    below the sum at it; draw 2 (index 133 829, not chosen) 2.1e-5 and 4.1e-5; the summation order
+    can move a cumulative sum by at most n x 2^-53 = 2.9e-11 of the potential."""
+    ref = _kpp_big_reference()
+    o, bg = _kpp_big_device(G)
+    print(f"G={G}: centres {int(o[22])}/{ref['info']['center0']:.0f} {int(o[23])}/{ref['info']['center1']:.0f} "
+          f"km {int(o[19])}/{ref['info']['kmeans_iter']:.0f} em {int(o[20])}/{ref['info']['em_iter']:.0f} "
+          f"dt {np.abs(o[0:3] - ref['t']).max():.3e} dR {np.abs(o[7:16].reshape(3, 3) - ref['R']).max():.3e}")
+    assert o[16] == ref["rc"] == 0
+    assert int(o[22]) == int(ref["info"]["center0"]) and int(o[23]) == int(ref["info"]["center1"])
+    assert int(o[19]) == int(ref["info"]["kmeans_iter"]) and int(o[20]) == int(ref["info"]["em_iter"])
+    agree = (bg == ref["bg_mask"]).mean()
+    assert agree >= 0.999, agree
+    assert np.abs(o[0:3] - ref["t"]).max() < 1e-5
+    assert np.abs(o[7:16].reshape(3, 3) - ref["R"]).max() < 1e-6
+    o1, _ = _kpp_big_device(1)
+    assert [int(v) for v in o[[22, 23, 19, 20]]] == [int(v) for v in o1[[22, 23, 19, 20]]]
 
 
 def test_concurrent_streams_one_context(dev):
@@ -475,7 +536,7 @@ def test_slove_RT_by_SVD_float32(oracle, dev):
 
 
 def test_frame_above_32bit_offsets_rejected(dev):
-    """The streaming loops address a frame with 32-bit byte offsets (mask_pose.hip load3_off):
+    """The streaming loops address a frame with 32-bit byte offsets (mask_common.hpp load3_off):
     ssf_mask_pose_batch rejects a frame above 2^32 / 12 points (f32) or 2^32 / 24 (f64) with
     SSF_E_ARG before anything is launched (the device pointers are never dereferenced here)."""
     import ctypes as C
