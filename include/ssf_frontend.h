@@ -643,6 +643,58 @@ int32_t ssf_pose_graph_batch_robust(ssf_ctx* ctx, void* stream, int32_t n_graphs
                                     double* d_stats, double* d_cost_log,
                                     const ssf_pgo_robust* robust, double* d_edge_out);
 
+/* ssf_pose_graph_batch_lm is ssf_pose_graph_batch_robust with Levenberg-Marquardt step control
+ * (Ceres' LevenbergMarquardtStrategy, the step rule of the front-end's solve): no step is taken
+ * that does not lower the cost.  One attempt solves (H + D / radius) dx = -g, H = J^T J over every
+ * factor (the loop rows scaled by the loss), D = diag(H) clamped to [1e-6, 1e32], and evaluates
+ * the trial point X (+) dx.  With mcc = -(g^T dx + dx^T H dx / 2), the decrease the model promises,
+ * and rho = (cost - trial cost) / mcc:
+ *   rho > min_relative_decrease   accepted: radius = min(radius / max(1/3, 1 - (2 rho - 1)^3),
+ *                                 max_radius), the divisor of the next rejection back to 2; stops
+ *                                 with SSF_PGO_CONVERGED when func_tol > 0 and the cost fell by no
+ *                                 more than func_tol * (the cost before)
+ *   otherwise (a NaN trial cost too)   rejected: radius /= divisor, divisor *= 2; X stays
+ *   a failed Cholesky pivot of the damped system, a non-finite step or not (mcc > 0)   invalid:
+ *                                 radius and divisor as for a rejection, no trial point
+ * params->max_iter bounds the attempts.  The solve also ends (SSF_PGO_OK) after more than five
+ * invalid attempts in a row or when a rejection or acceptance leaves radius < min_radius.  The
+ * poses written back are the last accepted point, so SSF_PGO_OUT_COST <= SSF_PGO_OUT_COST0;
+ * SSF_PGO_OUT_ITERATIONS counts the attempts, SSF_PGO_OUT_DX is the max-norm of the last accepted
+ * step (0: none), SSF_PGO_OUT_ACCEPTED the accepted attempts, SSF_PGO_OUT_RADIUS the final radius
+ * (these two are 0 from the other entry points); d_cost_log[a] is the cost after attempt a, so it
+ * never rises (a rejected or invalid attempt repeats the entry before it); d_edge_out belongs to
+ * the last accepted point.  A missing chain link still ends with SSF_PGO_NOT_PD.
+ *   lm        nullable: with d_lm_log NULL too this is ssf_pose_graph_batch_robust itself, launch
+ *             for launch
+ *   d_lm_log  nullable; n_graphs * max_iter * SSF_PGO_LM_LOG_STRIDE doubles, per attempt the trial
+ *             cost (NaN for an invalid attempt), mcc (NaN when the step itself failed), the radius
+ *             after the attempt and the outcome (SSF_PGO_LM_*); NaN for the attempts not made and
+ *             for every attempt of a graph that ends with SSF_PGO_EMPTY, _BAD_INPUT,
+ *             _TOO_MANY_LOOPS or _NOT_PD
+ * SSF_E_ARG (before any HIP call) as ssf_pose_graph_batch_robust, and on radius0, max_radius or
+ * min_radius not finite or <= 0, min_radius > max_radius, min_relative_decrease outside [0, 1),
+ * or d_lm_log without lm. */
+typedef struct {
+    double radius0;                 /* 1e4: Ceres' initial_trust_region_radius                 */
+    double min_relative_decrease;   /* 1e-3                                                    */
+    double max_radius;              /* 1e16                                                    */
+    double min_radius;              /* 1e-32                                                   */
+} ssf_pgo_lm;
+enum { SSF_PGO_OUT_ACCEPTED = 6, SSF_PGO_OUT_RADIUS = 7 };
+#define SSF_PGO_LM_LOG_STRIDE 4
+enum { SSF_PGO_LM_LOG_COST = 0, SSF_PGO_LM_LOG_MCC = 1, SSF_PGO_LM_LOG_RADIUS = 2, SSF_PGO_LM_LOG_OUTCOME = 3 };
+enum { SSF_PGO_LM_REJECTED = 0, SSF_PGO_LM_ACCEPTED = 1, SSF_PGO_LM_INVALID = 2 };
+int32_t ssf_pgo_lm_default(ssf_pgo_lm* out);
+int32_t ssf_pose_graph_batch_lm(ssf_ctx* ctx, void* stream, int32_t n_graphs, double* d_pose,
+                                const int32_t* d_node_off, const int32_t* h_node_off,
+                                const int32_t* d_edge_ij, const double* d_edge_meas,
+                                const double* d_edge_var, const int32_t* d_edge_off,
+                                const int32_t* h_edge_off, const double* d_prior_pose,
+                                const double* d_prior_var, const ssf_pgo_params* params,
+                                double* d_stats, double* d_cost_log,
+                                const ssf_pgo_robust* robust, double* d_edge_out,
+                                const ssf_pgo_lm* lm, double* d_lm_log);
+
 #ifdef __cplusplus
 }
 #endif

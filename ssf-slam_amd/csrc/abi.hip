@@ -1097,7 +1097,7 @@ int32_t ssf_pgo_robust_default(int32_t kind, ssf_pgo_robust* out) {
     return SSF_OK;
 }
 
-// both pose-graph entry points; robust: the loss kernels and the per-edge output
+// the pose-graph entry points; robust: the loss kernels and the per-edge output; lm: step control
 static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
                                 const int32_t* d_node_off, const int32_t* h_node_off,
                                 const int32_t* d_edge_ij, const double* d_edge_meas,
@@ -1105,7 +1105,7 @@ static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, doub
                                 const int32_t* h_edge_off, const double* d_prior_pose,
                                 const double* d_prior_var, const ssf_pgo_params* prm,
                                 double* d_stats, double* d_cost_log, bool robust, int rkind, double rk,
-                                double* d_edge_out);
+                                double* d_edge_out, const ssf_pgo_lm* lm, double* d_lm_log);
 
 int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
                              const int32_t* d_node_off, const int32_t* h_node_off,
@@ -1116,7 +1116,7 @@ int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double*
                              double* d_stats, double* d_cost_log) {
     return pose_graph_batch(c, stream, n_graphs, d_pose, d_node_off, h_node_off, d_edge_ij, d_edge_meas,
                             d_edge_var, d_edge_off, h_edge_off, d_prior_pose, d_prior_var, prm, d_stats,
-                            d_cost_log, false, SSF_PGO_ROBUST_NONE, 0.0, nullptr);
+                            d_cost_log, false, SSF_PGO_ROBUST_NONE, 0.0, nullptr, nullptr, nullptr);
 }
 
 int32_t ssf_pose_graph_batch_robust(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
@@ -1127,18 +1127,49 @@ int32_t ssf_pose_graph_batch_robust(ssf_ctx* c, void* stream, int32_t n_graphs, 
                                     const double* d_prior_var, const ssf_pgo_params* prm,
                                     double* d_stats, double* d_cost_log, const ssf_pgo_robust* robust,
                                     double* d_edge_out) {
+    return ssf_pose_graph_batch_lm(c, stream, n_graphs, d_pose, d_node_off, h_node_off, d_edge_ij, d_edge_meas,
+                                   d_edge_var, d_edge_off, h_edge_off, d_prior_pose, d_prior_var, prm, d_stats,
+                                   d_cost_log, robust, d_edge_out, nullptr, nullptr);
+}
+
+int32_t ssf_pgo_lm_default(ssf_pgo_lm* out) {
+    if (!out) return SSF_E_ARG;
+    out->radius0 = 1e4;             // Ceres' LevenbergMarquardtStrategy, as the front-end's solve
+    out->min_relative_decrease = 1e-3;
+    out->max_radius = 1e16;
+    out->min_radius = 1e-32;
+    return SSF_OK;
+}
+
+int32_t ssf_pose_graph_batch_lm(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
+                                const int32_t* d_node_off, const int32_t* h_node_off,
+                                const int32_t* d_edge_ij, const double* d_edge_meas,
+                                const double* d_edge_var, const int32_t* d_edge_off,
+                                const int32_t* h_edge_off, const double* d_prior_pose,
+                                const double* d_prior_var, const ssf_pgo_params* prm,
+                                double* d_stats, double* d_cost_log, const ssf_pgo_robust* robust,
+                                double* d_edge_out, const ssf_pgo_lm* lm, double* d_lm_log) {
     if (!c) return SSF_E_ARG;
+    if (lm) {
+        auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+        if (!pos(lm->radius0) || !pos(lm->max_radius) || !pos(lm->min_radius) || lm->min_radius > lm->max_radius)
+            return fail(c, SSF_E_ARG, "pose_graph_batch_lm: radii must be finite, positive and min <= max");
+        if (!(lm->min_relative_decrease >= 0.0 && lm->min_relative_decrease < 1.0))
+            return fail(c, SSF_E_ARG, "pose_graph_batch_lm: min_relative_decrease must lie in [0, 1)");
+    } else if (d_lm_log) {
+        return fail(c, SSF_E_ARG, "pose_graph_batch_lm: d_lm_log needs lm");
+    }
     const int rkind = robust ? robust->kind : SSF_PGO_ROBUST_NONE;
     if (rkind < SSF_PGO_ROBUST_NONE || rkind > SSF_PGO_ROBUST_GEMAN_MCCLURE)
         return fail(c, SSF_E_ARG, "pose_graph_batch_robust: unknown loss kind");
     if (rkind != SSF_PGO_ROBUST_NONE && !(std::isfinite(robust->k) && robust->k > 0.0))
         return fail(c, SSF_E_ARG, "pose_graph_batch_robust: k must be finite and positive");
-    // no loss and no per-edge output: the plain kernels, launch for launch
-    const bool plain = rkind == SSF_PGO_ROBUST_NONE && !d_edge_out;
+    // no loss, no per-edge output and no step control: the plain kernels, launch for launch
+    const bool plain = rkind == SSF_PGO_ROBUST_NONE && !d_edge_out && !lm;
     return pose_graph_batch(c, stream, n_graphs, d_pose, d_node_off, h_node_off, d_edge_ij, d_edge_meas,
                             d_edge_var, d_edge_off, h_edge_off, d_prior_pose, d_prior_var, prm, d_stats,
                             d_cost_log, !plain, rkind, rkind != SSF_PGO_ROBUST_NONE ? robust->k : 0.0,
-                            d_edge_out);
+                            d_edge_out, lm, d_lm_log);
 }
 
 static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
@@ -1148,7 +1179,7 @@ static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, doub
                                 const int32_t* h_edge_off, const double* d_prior_pose,
                                 const double* d_prior_var, const ssf_pgo_params* prm,
                                 double* d_stats, double* d_cost_log, bool robust, int rkind, double rk,
-                                double* d_edge_out) {
+                                double* d_edge_out, const ssf_pgo_lm* lm, double* d_lm_log) {
     if (!c) return SSF_E_ARG;
     if (n_graphs < 0 || !prm || prm->max_iter < 0 || prm->max_iter > SSF_PGO_MAX_ITER ||
         !(prm->func_tol >= 0.0) ||
@@ -1172,7 +1203,7 @@ static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, doub
         G.wide = ssf::pgo_graph_wide(G.K, G.E);
         (G.wide ? any_wide : any_narrow) = true;
         G.scratch_off = (int64_t)total;
-        total += ssf::pgo_graph_doubles(G.K, G.E, G.lcap, G.wide != 0);
+        total += ssf::pgo_graph_doubles(G.K, G.E, G.lcap, G.wide != 0, lm != nullptr);
     }
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(c, stream);
@@ -1182,7 +1213,12 @@ static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, doub
     SSF_TRY_HIP(c, hipMemcpyAsync(c->pgo_desc.p, c->pgo_h.data(), sizeof(ssf::PgoGraph) * (size_t)n_graphs,
                                   hipMemcpyHostToDevice, s), "H2D pose-graph descriptors");
     hipError_t e;
-    if (robust)
+    if (lm)
+        e = ssf::launch_pose_graph_lm(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose,
+                                      d_node_off, d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
+                                      d_prior_var, prm->max_iter, prm->func_tol, c->pgo_scratch.as<double>(),
+                                      d_stats, d_cost_log, rkind, rk, d_edge_out, *lm, d_lm_log);
+    else if (robust)
         e = ssf::launch_pose_graph_robust(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose,
                                           d_node_off, d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
                                           d_prior_var, prm->max_iter, prm->func_tol,

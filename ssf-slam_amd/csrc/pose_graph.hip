@@ -37,6 +37,9 @@
 //   edge's record is scaled by sqrt(w(s)), s its squared whitened residual, and it enters the cost
 //   with 2 rho(s).  Chain edges and the prior stay quadratic, so T is what it is without the loss.
 //   They also report every edge's weight and s (d_edge_out).
+//   k_pose_graph_lm / k_pose_graph_wide_lm are the loss kernels with Levenberg-Marquardt step control
+//   (ssf_pgo_lm): T is damped by D / radius, the step goes to a trial point, and only a trial that
+//   lowers the cost by enough of what the model promised becomes the point (see pgo_solve).
 //   No inter-work-group communication of any kind.  A graph writes its poses back only when it
 //   ends with SSF_PGO_OK / SSF_PGO_CONVERGED: it iterates on a copy in the context scratch.
 //   Every loop bound is a count the prologue validated (K, E from the host descriptor checked
@@ -60,12 +63,15 @@ static_assert(kPgoNarrowLoops <= SSF_PGO_MAX_LOOPS, "the narrow path is a subset
 
 bool pgo_graph_wide(int K, int E) { return E - (K - 1) > kPgoNarrowLoops; }
 
-size_t pgo_graph_doubles(int K, int E, int lcap, bool wide) {
+size_t pgo_graph_doubles(int K, int E, int lcap, bool wide, bool lm) {
     const size_t k = (size_t)K, nc = 6 * (size_t)lcap + 1, n = 6 * (size_t)lcap;
     const size_t head = 7 * k + (size_t)kPgoRec * ((size_t)E + 1) + 36 * k + 36 * k + 6 * k;
+    // step control: the trial poses and records, and (weight, s) of every edge at both points; they
+    // follow everything else, so the rest of the layout is the same with and without them
+    const size_t trial = lm ? 7 * k + (size_t)kPgoRec * ((size_t)E + 1) + 4 * (size_t)E : 0;
     // wide: the loop list (3 int32 a loop), one pass buffer, C, and the two capacitance vectors
-    if (wide) return head + 2 * (size_t)lcap + 6 * k * (size_t)kPgoThreads + n * n + 2 * n + 8;
-    return head + 6 * k * nc + n * n + 8;
+    if (wide) return head + 2 * (size_t)lcap + 6 * k * (size_t)kPgoThreads + n * n + 2 * n + trial + 8;
+    return head + 6 * k * nc + n * n + trial + 8;
 }
 
 SSF_DEV bool pgo_finite(double v) { return fabs(v) <= 1.79769313486231570e308; }   // false for NaN
@@ -304,14 +310,20 @@ SSF_DEV void pgo_substitute(const double* D, const double* O, int K, double* z, 
 // graph's scratch.  A work-group whose graph belongs to the other kernel returns at once.
 // kRobust: the loss (rkind, rk) on the loop edges, and edge_out (nullable): two doubles per edge
 // (SSF_PGO_EDGE_*) at the host's edge offsets, NaN for a graph that fails.
-template <bool kWide, bool kRobust>
+// kLM: Levenberg-Marquardt step control (ssf_pgo_lm; Ceres' LevenbergMarquardtStrategy, as k_solve's).
+// One pass of the loop is then one attempt: T gets D / radius on its diagonal (D: the clamped
+// diagonal of the full J^T J), the step goes to a trial copy of the poses, and the next pass
+// linearises the trial point and accepts it (the two pose and record buffers swap) or rejects it.
+// lm_log (nullable): SSF_PGO_LM_LOG_STRIDE doubles per attempt, NaN for a graph that fails.
+template <bool kWide, bool kRobust, bool kLM = false>
 SSF_DEV void pgo_solve(
     const PgoGraph* __restrict__ desc, double* __restrict__ pose, const int32_t* __restrict__ node_off,
     const int32_t* __restrict__ edge_ij, const double* __restrict__ edge_meas,
     const double* __restrict__ edge_var, const int32_t* __restrict__ edge_off,
     const double* __restrict__ prior_pose, const double* __restrict__ prior_var, int max_iter,
     double func_tol, double* scratch, double* __restrict__ stats, double* __restrict__ cost_log,
-    int rkind = 0, double rk = 0.0, double* __restrict__ edge_out = nullptr) {
+    int rkind = 0, double rk = 0.0, double* __restrict__ edge_out = nullptr, ssf_pgo_lm lm = ssf_pgo_lm{},
+    double* __restrict__ lm_log = nullptr) {
     __shared__ double red[kPgoThreads / 64];
     __shared__ double va[kWide ? 1 : kPgoMaxN], vb[kWide ? 1 : kPgoMaxN];
     __shared__ int2 ij_s[kPgoTile];
@@ -331,12 +343,16 @@ SSF_DEV void pgo_solve(
     const double kNaN = __builtin_nan("");
     // the host validated its edge offsets against each other: the call's output has E rows from edge0
     double* EO = kRobust && edge_out ? edge_out + (size_t)SSF_PGO_EDGE_OUT_STRIDE * (size_t)G.edge0 : nullptr;
+    double* LL = kLM && lm_log ? lm_log + (size_t)g * (size_t)max_iter * SSF_PGO_LM_LOG_STRIDE : nullptr;
 
     // ---- prologue: validation before any indexed access
     if (tid == 0) { bad_s = 0; nloop_s = 0; fail_s = 0; }
     __syncthreads();
     if (clog)
         for (int k = tid; k <= max_iter; k += kPgoThreads) clog[k] = kNaN;
+    if constexpr (kLM)
+        if (LL)
+            for (int k = tid; k < SSF_PGO_LM_LOG_STRIDE * max_iter; k += kPgoThreads) LL[k] = kNaN;
     int status = -1;
     if (K == 0) status = SSF_PGO_EMPTY;
     if (node_off[g] != G.node0 || node_off[g + 1] != G.node0 + K || edge_off[g] != G.edge0 ||
@@ -421,6 +437,12 @@ SSF_DEV void pgo_solve(
     double* VA = CM + 36 * (size_t)G.lcap * (size_t)G.lcap;      // wide: u, then w
     double* VB = VA + 6 * (size_t)G.lcap;
     const size_t zs = kWide ? (size_t)kPgoThreads : (size_t)NC;  // stride of a column's entries in Z
+    // step control: the trial point XT and its records RECT, and (weight, s) of every edge at the
+    // accepted point (WS) and at the trial point (WST); an accepted trial swaps the pairs
+    double* XT = kWide ? VB + 6 * (size_t)G.lcap : VA;
+    double* RECT = XT + 7 * (size_t)K;
+    double* WS = RECT + (size_t)kPgoRec * ((size_t)E + 1);
+    double* WST = WS + 2 * (size_t)E;
     for (int k = tid; k < K; k += kPgoThreads) {
         double q[4];
         pgo_quat_unit(P + 7 * (size_t)k, q);
@@ -432,18 +454,56 @@ SSF_DEV void pgo_solve(
     int iters = 0;
     double cost0 = 0.0, cost = 0.0, prev = 0.0, dxmax = 0.0;
     status = SSF_PGO_OK;
+    // step control, uniform over the work-group: the trust-region radius and the factor the next
+    // rejection divides it by, the run of invalid steps, the accepted steps, whether XT holds a
+    // trial point that waits for its evaluation, that step's model decrease and max-norm
+    double radius = lm.radius0, dec = 2.0, mcc = 0.0, dxt = 0.0;
+    int invalid = 0, accepted = 0;
+    bool trial = false;
+    // an attempt without a usable step (a pivot of the damped system failed, a non-finite step,
+    // no model decrease): the radius shrinks, the point stays -> true after more than 5 in a row
+    // (the body is discarded without kLM, so that it captures nothing there: a captured `cost` or
+    // `iters` changes the register allocation of the kernels without step control)
+    auto lm_invalid = [&](int it, double m) {
+        if constexpr (!kLM) {
+            return false;
+        } else {
+            radius /= dec;
+            dec *= 2.0;
+            trial = false;
+            iters = it + 1;
+            if (tid == 0) {
+                if (clog) clog[it + 1] = cost;
+                if (LL) {
+                    double* ll = LL + (size_t)SSF_PGO_LM_LOG_STRIDE * it;
+                    ll[SSF_PGO_LM_LOG_MCC] = m; ll[SSF_PGO_LM_LOG_RADIUS] = radius;
+                    ll[SSF_PGO_LM_LOG_OUTCOME] = SSF_PGO_LM_INVALID;
+                }
+            }
+            return ++invalid > 5;
+        }
+    };
     for (int it = 0; it <= max_iter; ++it) {
-        // -- linearise: factor E is the prior
+        // -- linearise: factor E is the prior.  Step control: pass 0 linearises the start, a later
+        //    pass the trial point of the attempt before it (none after an invalid attempt)
+        double* Xl = X;
+        double* Rl = REC;
+        double* Wl = WS;
+        bool lin = true;
+        if constexpr (kLM) {
+            if (it > 0) { Xl = XT; Rl = RECT; Wl = WST; }
+            lin = it == 0 || trial;
+        }
         double cs[1] = {0.0};
-        for (int e = tid; e <= E; e += kPgoThreads) {
-            double* rec = REC + (size_t)kPgoRec * e;
+        for (int e = lin ? tid : E + 1; e <= E; e += kPgoThreads) {
+            double* rec = Rl + (size_t)kPgoRec * e;
             if (e < E) {
-                const double* xi = X + 7 * (size_t)IJ[2 * e];
-                const double* xj = X + 7 * (size_t)IJ[2 * e + 1];
+                const double* xi = Xl + 7 * (size_t)IJ[2 * e];
+                const double* xj = Xl + 7 * (size_t)IJ[2 * e + 1];
                 pgo_linearise(xi, xi + 4, xj, xj + 4, ZM + 7 * (size_t)e, ZV + 6 * (size_t)e, rec);
             } else {
                 const double qi[4] = {0.0, 0.0, 0.0, 1.0}, ti[3] = {0.0, 0.0, 0.0};
-                pgo_linearise(qi, ti, X, X + 4, PP, PV, rec);
+                pgo_linearise(qi, ti, Xl, Xl + 4, PP, PV, rec);
             }
             double s = 0.0;
             for (int c = 0; c < 6; ++c) s += rec[c] * rec[c];
@@ -460,7 +520,10 @@ SSF_DEV void pgo_solve(
                         const double sw = sqrt(w);
                         for (int c = 0; c < kPgoRec; ++c) rec[c] *= sw;
                     }
-                    if (EO) {
+                    if constexpr (kLM) {               // edge_out gets the accepted point's at the end
+                        Wl[SSF_PGO_EDGE_OUT_STRIDE * (size_t)e + SSF_PGO_EDGE_WEIGHT] = w;
+                        Wl[SSF_PGO_EDGE_OUT_STRIDE * (size_t)e + SSF_PGO_EDGE_CHI2] = s;
+                    } else if (EO) {
                         EO[SSF_PGO_EDGE_OUT_STRIDE * (size_t)e + SSF_PGO_EDGE_WEIGHT] = w;
                         EO[SSF_PGO_EDGE_OUT_STRIDE * (size_t)e + SSF_PGO_EDGE_CHI2] = s;
                     }
@@ -471,12 +534,53 @@ SSF_DEV void pgo_solve(
             }
         }
         block_sum<1>(cs, red);                     // its barriers also publish REC
-        cost = 0.5 * cs[0];
-        if (tid == 0 && clog) clog[it] = cost;
-        if (it == 0) cost0 = cost;
-        if (it == max_iter) break;                 // the evaluation after the last retraction
-        if (it > 0 && func_tol > 0.0 && fabs(prev - cost) <= func_tol * prev) { status = SSF_PGO_CONVERGED; break; }
-        prev = cost;
+        if constexpr (!kLM) {
+            cost = 0.5 * cs[0];
+            if (tid == 0 && clog) clog[it] = cost;
+            if (it == 0) cost0 = cost;
+            if (it == max_iter) break;                 // the evaluation after the last retraction
+            if (it > 0 && func_tol > 0.0 && fabs(prev - cost) <= func_tol * prev) { status = SSF_PGO_CONVERGED; break; }
+            prev = cost;
+        } else {
+            if (it == 0) {
+                cost = cost0 = 0.5 * cs[0];
+                if (tid == 0 && clog) clog[0] = cost;
+            } else if (trial) {
+                // -- attempt `it` ends: accept the trial point when the cost fell by more than
+                //    min_relative_decrease of what the model promised (a NaN trial cost rejects)
+                const double ct = 0.5 * cs[0], rho = (cost - ct) / mcc;
+                const bool acc = rho > lm.min_relative_decrease;
+                bool stop = false;
+                if (acc) {
+                    prev = cost;
+                    cost = ct;
+                    double* sw = X; X = XT; XT = sw;
+                    sw = REC; REC = RECT; RECT = sw;
+                    sw = WS; WS = WST; WST = sw;
+                    ++accepted;
+                    dxmax = dxt;
+                    const double t = 2.0 * rho - 1.0;
+                    radius = fmin(radius / fmax(1.0 / 3.0, 1.0 - t * t * t), lm.max_radius);
+                    dec = 2.0;
+                    if (func_tol > 0.0 && prev - cost <= func_tol * prev) { status = SSF_PGO_CONVERGED; stop = true; }
+                } else {
+                    radius /= dec;
+                    dec *= 2.0;
+                }
+                trial = false;
+                if (tid == 0) {
+                    if (clog) clog[it] = cost;
+                    if (LL) {
+                        double* ll = LL + (size_t)SSF_PGO_LM_LOG_STRIDE * (it - 1);
+                        ll[SSF_PGO_LM_LOG_COST] = ct; ll[SSF_PGO_LM_LOG_MCC] = mcc;
+                        ll[SSF_PGO_LM_LOG_RADIUS] = radius;
+                        ll[SSF_PGO_LM_LOG_OUTCOME] = acc ? SSF_PGO_LM_ACCEPTED : SSF_PGO_LM_REJECTED;
+                    }
+                }
+                if (stop || radius < lm.min_radius) break;
+            }
+            if (it == max_iter) break;
+        }
 
         // -- assemble T (D, O) and the gradient, one thread per node, edges in order; the edge
         //    index pairs are staged through LDS in tiles, so the scan reads no global memory
@@ -486,6 +590,7 @@ SSF_DEV void pgo_solve(
             double Dk[36], Ok[36], gk[6];
             for (int c = 0; c < 36; ++c) { Dk[c] = 0.0; Ok[c] = 0.0; }
             for (int c = 0; c < 6; ++c) gk[c] = 0.0;
+            double hd[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // step control: the loop rows' part of diag(J^T J)
             bool linked = false;
             auto add = [&](int e, int i, int j) {      // factor e touches node k (e < 0: the prior)
                 const double* rec = REC + (size_t)kPgoRec * (e < 0 ? E : e);
@@ -510,6 +615,12 @@ SSF_DEV void pgo_solve(
 #pragma unroll
                             for (int b = 0; b <= a; ++b) Dk[6 * a + b] += jk[a] * jk[b];
                     }
+                    if constexpr (kLM) {
+                        if (!chain) {
+#pragma unroll
+                            for (int a = 0; a < 6; ++a) hd[a] += jk[a] * jk[a];
+                        }
+                    }
                     if (next) {
 #pragma unroll
                         for (int a = 0; a < 6; ++a) {
@@ -532,6 +643,12 @@ SSF_DEV void pgo_solve(
                         const int2 ij = ij_s[t];
                         if (ij.x == k || ij.y == k) add(e0 + t, ij.x, ij.y);
                     }
+            }
+            if constexpr (kLM) {
+                // H + D / radius, D = the diagonal of the full J^T J (chain edges, prior and the scaled
+                // loop rows) clamped to [1e-6, 1e32]: it lands on T, the Woodbury form stays
+#pragma unroll
+                for (int a = 0; a < 6; ++a) Dk[7 * a] += fmin(fmax(Dk[7 * a] + hd[a], 1e-6), 1e32) / radius;
             }
             if (act) {
                 for (int c = 0; c < 36; ++c) { D[36 * (size_t)k + c] = Dk[c]; O[36 * (size_t)k + c] = Ok[c]; }
@@ -612,10 +729,28 @@ SSF_DEV void pgo_solve(
                     for (int c = 0; c < 36; ++c) O[36 * (size_t)k + c] = M[c];
                 }
             }
-            if (!ok) fail_s = 1;
+            if constexpr (kLM) {
+                if (!ok) fail_s |= 2;                  // bit 0 stays the missing chain link's
+            } else {
+                if (!ok) fail_s = 1;
+            }
         }
         __syncthreads();
-        if (fail_s) { status = SSF_PGO_NOT_PD; break; }
+        if constexpr (kLM) {
+            // a missing chain link ends the graph as without step control (damping would make
+            // that singular T factorable); a failed pivot of the damped T is an invalid step
+            const int f = fail_s;
+            if (f & 1) { status = SSF_PGO_NOT_PD; break; }
+            if (f) {
+                __syncthreads();
+                if (tid == 0) fail_s = 0;
+                __syncthreads();
+                if (lm_invalid(it, kNaN)) break;
+                continue;
+            }
+        } else {
+            if (fail_s) { status = SSF_PGO_NOT_PD; break; }
+        }
 
         double mx = 0.0;
         if constexpr (!kWide) {
@@ -657,7 +792,14 @@ SSF_DEV void pgo_solve(
                     if (tid < n && tid >= j) CM[(size_t)j * n + tid] = tid == j ? sqrt(piv) : s / sqrt(piv);
                     __syncthreads();
                 }
-                if (status == SSF_PGO_NOT_PD) break;
+                if (status == SSF_PGO_NOT_PD) {
+                    if constexpr (kLM) {                           // a failed pivot of C: an invalid step
+                        status = SSF_PGO_OK;
+                        if (lm_invalid(it, kNaN)) break;
+                        continue;
+                    }
+                    break;
+                }
                 for (int j = 0; j < n; ++j) {                      // forward: va -> vb
                     __syncthreads();
                     const double yj = va[j] / CM[(size_t)j * n + j];
@@ -770,7 +912,14 @@ SSF_DEV void pgo_solve(
                     }
                     if (status == SSF_PGO_NOT_PD) break;
                 }
-                if (status == SSF_PGO_NOT_PD) break;
+                if (status == SSF_PGO_NOT_PD) {
+                    if constexpr (kLM) {
+                        status = SSF_PGO_OK;
+                        if (lm_invalid(it, kNaN)) break;
+                        continue;
+                    }
+                    break;
+                }
                 for (int j = 0; j < n; ++j) {                      // forward: VA -> VB
                     __syncthreads();
                     const double yj = VA[j] / CM[(size_t)j * n + j];
@@ -811,23 +960,59 @@ SSF_DEV void pgo_solve(
                     mx = pgo_finite(s) ? fmax(mx, fabs(s)) : __builtin_inf();
                 }
         }
-        dxmax = pgo_block_max(mx, red);
-        if (!pgo_finite(dxmax)) { status = SSF_PGO_NOT_PD; break; }
+        double* XO = X;                                // where the retraction writes
+        if constexpr (!kLM) {
+            dxmax = pgo_block_max(mx, red);
+            if (!pgo_finite(dxmax)) { status = SSF_PGO_NOT_PD; break; }
+        } else {
+            dxt = pgo_block_max(mx, red);
+            if (!pgo_finite(dxt)) {
+                if (lm_invalid(it, kNaN)) break;
+                continue;
+            }
+            // -- the model's decrease -(g^T dx + dx^T H dx / 2) = -sum_e (r_e . v_e + v_e . v_e / 2),
+            //    v_e = Ji dx_i + Jj dx_j from the records of X: one thread per factor, a fixed-order sum
+            double ms[1] = {0.0};
+            for (int e = tid; e <= E; e += kPgoThreads) {
+                const double* rec = REC + (size_t)kPgoRec * e;
+                const int i = e < E ? IJ[2 * e] : 0, j = e < E ? IJ[2 * e + 1] : 0;
+                double di[6], dj[6];
+                for (int q = 0; q < 6; ++q) {
+                    di[q] = e < E ? Z[(6 * (size_t)i + q) * zs] : 0.0;    // the prior has no Ji
+                    dj[q] = Z[(6 * (size_t)j + q) * zs];
+                }
+                for (int r = 0; r < 6; ++r) {
+                    double v = 0.0;
+                    for (int q = 0; q < 6; ++q) v += rec[6 + 6 * r + q] * di[q] + rec[42 + 6 * r + q] * dj[q];
+                    ms[0] -= rec[r] * v + 0.5 * v * v;
+                }
+            }
+            block_sum<1>(ms, red);
+            mcc = ms[0];
+            if (!(mcc > 0.0)) {
+                if (lm_invalid(it, mcc)) break;
+                continue;
+            }
+            invalid = 0;
+            trial = true;
+            XO = XT;
+        }
         for (int k = tid; k < K; k += kPgoThreads) {
             double d[6];
             for (int r = 0; r < 6; ++r) d[r] = Z[(6 * (size_t)k + r) * zs];
-            double* x = X + 7 * (size_t)k;
+            const double* x = X + 7 * (size_t)k;
+            double* xo = XO + 7 * (size_t)k;
             const double q[4] = {x[0], x[1], x[2], x[3]};
             double R[9];
             pgo_quat_R(q, R);
-            for (int r = 0; r < 3; ++r) x[4 + r] += R[3 * r] * d[3] + R[3 * r + 1] * d[4] + R[3 * r + 2] * d[5];
+            for (int r = 0; r < 3; ++r) xo[4 + r] = x[4 + r] + (R[3 * r] * d[3] + R[3 * r + 1] * d[4] + R[3 * r + 2] * d[5]);
             const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
             const double sc = th < 1e-8 ? 0.5 : sin(0.5 * th) / th;
             const double dq[4] = {sc * d[0], sc * d[1], sc * d[2], th < 1e-8 ? 1.0 : cos(0.5 * th)};
             double qn[4];
             quat_mul(q, dq, qn);
             pgo_quat_unit(qn, qn);
-            for (int c = 0; c < 4; ++c) x[c] = qn[c];
+            for (int c = 0; c < 4; ++c) xo[c] = qn[c];
         }
         __syncthreads();
         iters = it + 1;
@@ -839,12 +1024,19 @@ SSF_DEV void pgo_solve(
     if constexpr (kRobust)
         if (EO && status == SSF_PGO_NOT_PD)
             for (int e = tid; e < SSF_PGO_EDGE_OUT_STRIDE * E; e += kPgoThreads) EO[e] = kNaN;
+    if constexpr (kLM) {
+        if (EO && status != SSF_PGO_NOT_PD)            // (weight, s) at the last accepted point
+            for (int e = tid; e < SSF_PGO_EDGE_OUT_STRIDE * E; e += kPgoThreads) EO[e] = WS[e];
+        if (LL && status == SSF_PGO_NOT_PD)
+            for (int k = tid; k < SSF_PGO_LM_LOG_STRIDE * max_iter; k += kPgoThreads) LL[k] = kNaN;
+    }
     if (tid == 0) {
         const bool ok = status != SSF_PGO_NOT_PD;
         st[SSF_PGO_OUT_STATUS] = status; st[SSF_PGO_OUT_ITERATIONS] = ok ? iters : 0.0;
         st[SSF_PGO_OUT_COST0] = cost0; st[SSF_PGO_OUT_COST] = ok ? cost : kNaN;
         st[SSF_PGO_OUT_DX] = ok ? dxmax : 0.0; st[SSF_PGO_OUT_LOOPS] = L;
-        st[6] = 0.0; st[7] = 0.0;
+        st[SSF_PGO_OUT_ACCEPTED] = kLM && ok ? accepted : 0.0;
+        st[SSF_PGO_OUT_RADIUS] = kLM && ok ? radius : 0.0;
     }
 }
 
@@ -875,6 +1067,23 @@ __global__ __launch_bounds__(kPgoThreads) void k_pose_graph_wide_robust(SSF_PGO_
                                                                         double* __restrict__ edge_out) {
     pgo_solve<true, true>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var,
                           max_iter, func_tol, scratch, stats, cost_log, rkind, rk, edge_out);
+}
+
+// Step control: the loss kernels' arguments (kind none is weight 1), then the strategy and its log.
+__global__ __launch_bounds__(kPgoThreads) void k_pose_graph_lm(SSF_PGO_KERNEL_ARGS, int rkind, double rk,
+                                                               double* __restrict__ edge_out, ssf_pgo_lm lm,
+                                                               double* __restrict__ lm_log) {
+    pgo_solve<false, true, true>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose,
+                                 prior_var, max_iter, func_tol, scratch, stats, cost_log, rkind, rk, edge_out, lm,
+                                 lm_log);
+}
+
+__global__ __launch_bounds__(kPgoThreads) void k_pose_graph_wide_lm(SSF_PGO_KERNEL_ARGS, int rkind, double rk,
+                                                                    double* __restrict__ edge_out, ssf_pgo_lm lm,
+                                                                    double* __restrict__ lm_log) {
+    pgo_solve<true, true, true>(desc, pose, node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose,
+                                prior_var, max_iter, func_tol, scratch, stats, cost_log, rkind, rk, edge_out, lm,
+                                lm_log);
 }
 
 // Both kernels run over every graph of the batch; a work-group returns at once when its graph
@@ -919,6 +1128,29 @@ hipError_t launch_pose_graph_robust(hipStream_t s, int n_graphs, bool any_narrow
         hipLaunchKernelGGL(k_pose_graph_wide_robust, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose,
                            node_off, edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter,
                            func_tol, scratch, stats, cost_log, rkind, rk, edge_out);
+    }
+    return hipGetLastError();
+}
+
+// The same dispatch onto the kernels with step control; the scratch is sized with lm = true.
+hipError_t launch_pose_graph_lm(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide, const PgoGraph* desc,
+                                double* pose, const int32_t* node_off, const int32_t* edge_ij,
+                                const double* edge_meas, const double* edge_var, const int32_t* edge_off,
+                                const double* prior_pose, const double* prior_var, int max_iter, double func_tol,
+                                double* scratch, double* stats, double* cost_log, int rkind, double rk,
+                                double* edge_out, const ssf_pgo_lm& lm, double* lm_log) {
+    if (n_graphs <= 0) return hipSuccess;
+    if (any_narrow) {
+        kmark(s, "k_pose_graph_lm");
+        hipLaunchKernelGGL(k_pose_graph_lm, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose, node_off, edge_ij,
+                           edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter, func_tol, scratch,
+                           stats, cost_log, rkind, rk, edge_out, lm, lm_log);
+    }
+    if (any_wide) {
+        kmark(s, "k_pose_graph_wide_lm");
+        hipLaunchKernelGGL(k_pose_graph_wide_lm, dim3(n_graphs), dim3(kPgoThreads), 0, s, desc, pose, node_off,
+                           edge_ij, edge_meas, edge_var, edge_off, prior_pose, prior_var, max_iter, func_tol,
+                           scratch, stats, cost_log, rkind, rk, edge_out, lm, lm_log);
     }
     return hipGetLastError();
 }

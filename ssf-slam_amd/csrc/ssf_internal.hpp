@@ -321,7 +321,7 @@ struct PgoGraph {             // one per graph, built on the host from the host 
     int32_t wide;             // pgo_graph_wide(K, E): solved by k_pose_graph_wide
 };
 bool pgo_graph_wide(int K, int E);      // more than 32 edges beyond K - 1: it may hold more than 32 loops
-size_t pgo_graph_doubles(int K, int E, int lcap, bool wide);
+size_t pgo_graph_doubles(int K, int E, int lcap, bool wide, bool lm);   // lm: with the trial buffers
 hipError_t launch_pose_graph(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
                              const PgoGraph* desc, double* pose,
                              const int32_t* node_off, const int32_t* edge_ij, const double* edge_meas,
@@ -335,5 +335,13 @@ hipError_t launch_pose_graph_robust(hipStream_t s, int n_graphs, bool any_narrow
                                     const int32_t* edge_off, const double* prior_pose, const double* prior_var,
                                     int max_iter, double func_tol, double* scratch, double* stats,
                                     double* cost_log, int rkind, double rk, double* edge_out);
+// the loss kernels with step control (ssf_pgo_lm); lm_log is nullable
+hipError_t launch_pose_graph_lm(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
+                                const PgoGraph* desc, double* pose, const int32_t* node_off,
+                                const int32_t* edge_ij, const double* edge_meas, const double* edge_var,
+                                const int32_t* edge_off, const double* prior_pose, const double* prior_var,
+                                int max_iter, double func_tol, double* scratch, double* stats,
+                                double* cost_log, int rkind, double rk, double* edge_out, const ssf_pgo_lm& lm,
+                                double* lm_log);
 
 }  // namespace ssf

@@ -42,6 +42,7 @@ EXPORTS = [
     "ssf_set_mask_schedule", "ssf_register_plan", "ssf_pgo_params_default", "ssf_pose_graph_batch",
     "ssf_transform_clouds_batch", "ssf_subsample_batch",
     "ssf_pgo_robust_default", "ssf_pose_graph_batch_robust",
+    "ssf_pgo_lm_default", "ssf_pose_graph_batch_lm",
 ]
 # ssf_subsample_batch: limits and per-frame status codes
 SAMPLE_MAX_NB, SAMPLE_MAX_POINTS = 8192, 1 << 24
@@ -64,7 +65,7 @@ ICP_STATES = {0: "not_converged", 1: "iterations", 2: "transform", 3: "abs_mse",
 
 
 PGO_MAX_LOOPS, PGO_MAX_ITER, PGO_OUT_STRIDE = 256, 1024, 8
-PGO_OUT = dict(STATUS=0, ITERATIONS=1, COST0=2, COST=3, DX=4, LOOPS=5)
+PGO_OUT = dict(STATUS=0, ITERATIONS=1, COST0=2, COST=3, DX=4, LOOPS=5, ACCEPTED=6, RADIUS=7)
 PGO_OK, PGO_CONVERGED, PGO_EMPTY, PGO_BAD_INPUT, PGO_TOO_MANY_LOOPS, PGO_NOT_PD = range(6)
 PGO_STATUS = {0: "ok", 1: "converged", 2: "empty", 3: "bad_input", 4: "too_many_loops", 5: "not_pd"}
 
@@ -74,6 +75,10 @@ PGO_ROBUST_NONE, PGO_ROBUST_HUBER, PGO_ROBUST_CAUCHY, PGO_ROBUST_GEMAN_MCCLURE =
 PGO_ROBUST_KINDS = dict(none=0, huber=1, cauchy=2, geman_mcclure=3)
 PGO_EDGE_OUT_STRIDE = 2
 PGO_EDGE_OUT = dict(WEIGHT=0, CHI2=1)
+# ssf_pgo_lm: step control (ssf_pose_graph_batch_lm) and its per-attempt log
+PGO_LM_LOG_STRIDE = 4
+PGO_LM_LOG = dict(COST=0, MCC=1, RADIUS=2, OUTCOME=3)
+PGO_LM_REJECTED, PGO_LM_ACCEPTED, PGO_LM_INVALID = range(3)
 
 
 class PgoParams(C.Structure):
@@ -82,6 +87,11 @@ class PgoParams(C.Structure):
 
 class PgoRobust(C.Structure):
     _fields_ = [("kind", C.c_int32), ("k", C.c_double)]
+
+
+class PgoLm(C.Structure):
+    _fields_ = [("radius0", C.c_double), ("min_relative_decrease", C.c_double), ("max_radius", C.c_double),
+                ("min_radius", C.c_double)]
 
 
 class IcpParams(C.Structure):
@@ -219,6 +229,12 @@ def lib():
     L.ssf_pose_graph_batch_robust.argtypes = [vp, vp, i32] + [vp] * 10 + [C.POINTER(PgoParams), vp, vp,
                                                                           C.POINTER(PgoRobust), vp]
     L.ssf_pose_graph_batch_robust.restype = i32
+    L.ssf_pgo_lm_default.argtypes = [C.POINTER(PgoLm)]
+    L.ssf_pgo_lm_default.restype = i32
+    L.ssf_pose_graph_batch_lm.argtypes = [vp, vp, i32] + [vp] * 10 + [C.POINTER(PgoParams), vp, vp,
+                                                                      C.POINTER(PgoRobust), vp,
+                                                                      C.POINTER(PgoLm), vp]
+    L.ssf_pose_graph_batch_lm.restype = i32
     L.ssf_pn2_last_error.argtypes = []
     L.ssf_pn2_last_error.restype = C.c_char_p
     L.ssf_pn2_furthest_point_sample.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]

@@ -12,7 +12,8 @@ noise = the ICP fitness score).  By default the published pose is the loop-adjus
 the pose graph on the GPU at every loop closure (``optimize_pose_graphs`` <- runOptimize
 :280-293, batched Gauss-Newton in pose_graph.hip, not GTSAM's iSAM2) and rewrites every
 keyframe pose (correctPoses :296-332); ``robust=pgo_robust("huber")`` puts
-a robust loss on the loop edges of those solves.  ``LoopCloser(map_cloud=True)`` also keeps the
+a robust loss on the loop edges of those solves and ``lm=pgo_lm()`` Levenberg-Marquardt step
+control under them (``pgo=pgo_params(...)`` their iteration limit).  ``LoopCloser(map_cloud=True)`` also keeps the
 accumulated map cloud (mapCloudPtr: updateKeyPose :309-311, the rebuild of
 correctPoses :320-325) on the device in an ``ssf.MapCloud``; a new keyframe
 goes into the map at its stored key pose (the reference places it at its iSAM2 estimate).
@@ -163,7 +164,38 @@ def parse_robust(text):
     return pgo_robust(kind, k if sep else None)
 
 
-def optimize_pose_graphs(fe: Frontend, graphs, params=None, robust=None, edge_out=False):
+def pgo_lm(radius0=1e4, min_relative_decrease=1e-3, max_radius=1e16, min_radius=1e-32):
+    """Levenberg-Marquardt step control for the pose-graph solve (ssf_pgo_lm; Ceres'
+    LevenbergMarquardtStrategy and its defaults): no step is taken that raises the cost."""
+    p = _abi.PgoLm()
+    _abi.lib().ssf_pgo_lm_default(C.byref(p))
+    try:
+        vals = [float(v) for v in (radius0, min_relative_decrease, max_radius, min_radius)]
+    except (TypeError, ValueError):
+        raise ValueError("pgo_lm: the parameters are numbers") from None
+    p.radius0, p.min_relative_decrease, p.max_radius, p.min_radius = vals
+    if not all(math.isfinite(v) and v > 0.0 for v in (p.radius0, p.max_radius, p.min_radius)):
+        raise ValueError("pgo_lm: radius0, max_radius and min_radius must be finite and positive")
+    if p.min_radius > p.max_radius:
+        raise ValueError("pgo_lm: min_radius is above max_radius")
+    if not 0.0 <= p.min_relative_decrease < 1.0:
+        raise ValueError("pgo_lm: min_relative_decrease must lie in [0, 1)")
+    return p
+
+
+def parse_lm(text):
+    """The value of --map-lm[=RADIUS0] (True: no value) -> pgo_lm(RADIUS0)."""
+    if text is True:
+        return pgo_lm()
+    try:
+        r0 = float(text)
+    except (TypeError, ValueError):
+        raise ValueError(f"step control {text!r}: RADIUS0 must be a number") from None
+    return pgo_lm(radius0=r0)
+
+
+def optimize_pose_graphs(fe: Frontend, graphs, params=None, robust=None, edge_out=False, lm=None,
+                         lm_log=False):
     """Batched pose-graph optimisation, one launch for every graph of the list.  A graph is a
     dict(poses [K, 7] f64 (q xyzw, t), edge_ij [E, 2] graph-local, edge_meas [E, 7], edge_var
     [E, 6] (rotation then translation), prior_pose [7], prior_var [6] on node 0).
@@ -171,7 +203,14 @@ def optimize_pose_graphs(fe: Frontend, graphs, params=None, robust=None, edge_ou
     cost_log).  A graph whose status is not ok / converged gets its poses back unchanged.
     robust (pgo_robust): a loss on the loop edges (|i - j| != 1); with it or with edge_out every
     result also carries edge_weight [E] and edge_chi2 [E] (the unweighted squared whitened
-    residual) of the evaluation `cost` belongs to, NaN for a graph that failed."""
+    residual) of the evaluation `cost` belongs to, NaN for a graph that failed.
+    lm (pgo_lm): Levenberg-Marquardt step control; params.max_iter then bounds the attempts,
+    iterations counts them, poses / cost / dx belong to the last accepted point, cost_log never
+    rises, and every result also holds accepted (the accepted attempts) and radius (the final
+    trust-region radius).  lm_log (needs lm): also lm_log [attempts, 4], per attempt the trial cost,
+    the model's decrease, the radius after it and the outcome (PGO_LM_LOG / PGO_LM_*)."""
+    if lm_log and lm is None:
+        raise ValueError("lm_log is the log of the step control: it needs lm")
     G = len(graphs)
     if G == 0:
         return []
@@ -204,7 +243,18 @@ def optimize_pose_graphs(fe: Frontend, graphs, params=None, robust=None, edge_ou
     args = (fe._h, _stream(dev), G, _ptr(d_pose), _ptr(d_noff), C.c_void_p(h_noff.data_ptr()), _ptr(d_ij),
             _ptr(d_meas), _ptr(d_var), _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(d_prior), _ptr(d_pvar),
             C.byref(params), _ptr(stats), _ptr(clog))
-    if with_edges:
+    if lm is not None:
+        eout = (torch.zeros(int(h_eoff[-1]) + 1, _abi.PGO_EDGE_OUT_STRIDE, dtype=torch.float64, device=dev)
+                if with_edges else None)
+        llog = (torch.zeros(G, max(params.max_iter, 1), _abi.PGO_LM_LOG_STRIDE, dtype=torch.float64, device=dev)
+                if lm_log else None)
+        fe._check(_abi.lib().ssf_pose_graph_batch_lm(*args, None if robust is None else C.byref(robust),
+                                                     None if eout is None else _ptr(eout), C.byref(lm),
+                                                     None if llog is None else _ptr(llog)),
+                  "ssf_pose_graph_batch_lm")
+        eo = None if eout is None else eout.cpu().numpy()
+        ll = None if llog is None else llog.cpu().numpy()
+    elif with_edges:
         eout = torch.zeros(int(h_eoff[-1]) + 1, _abi.PGO_EDGE_OUT_STRIDE, dtype=torch.float64, device=dev)
         fe._check(_abi.lib().ssf_pose_graph_batch_robust(*args, None if robust is None else C.byref(robust),
                                                          _ptr(eout)), "ssf_pose_graph_batch_robust")
@@ -226,6 +276,10 @@ def optimize_pose_graphs(fe: Frontend, graphs, params=None, robust=None, edge_ou
             rows = eo[int(h_eoff[k]):int(h_eoff[k + 1])]
             res[-1].update(edge_weight=rows[:, _abi.PGO_EDGE_OUT["WEIGHT"]].copy(),
                            edge_chi2=rows[:, _abi.PGO_EDGE_OUT["CHI2"]].copy())
+        if lm is not None:
+            res[-1].update(accepted=int(o[_abi.PGO_OUT["ACCEPTED"]]), radius=float(o[_abi.PGO_OUT["RADIUS"]]))
+            if lm_log:
+                res[-1]["lm_log"] = ll[k, :res[-1]["iterations"]].copy()
     return res
 
 
@@ -295,6 +349,10 @@ class LoopCloser:
     # weight of every edge (loop_weights).  Nothing is rejected: a down-weighted loop stays in
     # the graph and its correction stays in trans_loop_adjust
     robust: object | None = None
+    # step control of every solve (pgo_lm), and the parameters of the solves (pgo_params; None:
+    # the defaults, max_iter 8 -- few attempts for step control from a far start)
+    lm: object | None = None
+    pgo: object | None = None
     # map_cloud=True: the keyframe clouds live in a device store and the accumulated map
     # (mapCloudPtr, updateKeyPose :309-311) is kept equal to every keyframe under its current key
     # pose: appended per keyframe, rebuilt in one launch when the poses are rewritten
@@ -453,7 +511,9 @@ class LoopCloser:
         """runOptimize + correctPoses for one closed loop -> the corrected T_map_0_curr."""
         self.add_loop_edge(c)
         kw = {} if self.robust is None else dict(robust=self.robust, edge_out=True)
-        return self.apply_optimization(optimize_pose_graphs(self.fe, [self.pose_graph()], **kw)[0])
+        if self.lm is not None:
+            kw["lm"] = self.lm
+        return self.apply_optimization(optimize_pose_graphs(self.fe, [self.pose_graph()], self.pgo, **kw)[0])
 
     def loop_weights(self):
         """[(key_cur, key_pre, weight)] of the loop edges in the last solve, in graph order (a
@@ -465,13 +525,16 @@ class LoopCloser:
                 if abs(int(e[0]) - int(e[1])) != 1]
 
 
-def optimize_loop_closers(fe: Frontend, closers, constraints, params=None, robust=None):
+def optimize_loop_closers(fe: Frontend, closers, constraints, params=None, robust=None, lm=None):
     """Several sequences that closed a loop in the same step, solved in one launch: adds each
     constraint to its closer's graph, optimises all graphs together and applies correctPoses to
     each.  -> the corrected T_map_0_curr of every closer.  robust (pgo_robust): the loss on the
-    loop edges of every graph of the launch; the closers then hold the edge weights."""
+    loop edges of every graph of the launch; the closers then hold the edge weights.  lm (pgo_lm):
+    step control for every graph of the launch."""
     for lc, c in zip(closers, constraints):
         lc.add_loop_edge(c)
     kw = {} if robust is None else dict(robust=robust, edge_out=True)
+    if lm is not None:
+        kw["lm"] = lm
     res = optimize_pose_graphs(fe, [lc.pose_graph() for lc in closers], params, **kw)
     return [lc.apply_optimization(r) for lc, r in zip(closers, res)]

@@ -263,20 +263,32 @@ class MapOptimizationNode:
     keyframe pose (runOptimize / correctPoses, :280-332; ``closer.key6d``,
     ``closer.last_optimization``); the keyframe that closed the loop is published at its
     corrected pose.  map_robust (ssf.loop.pgo_robust, with optimize): a robust loss on the loop
-    edges of those solves; ``closer.loop_weights()`` then gives every loop's weight.
+    edges of those solves; ``closer.loop_weights()`` then gives every loop's weight.  map_lm
+    (ssf.loop.pgo_lm, with optimize): Levenberg-Marquardt step control for those solves; map_iters
+    (with optimize): their max_iter (default 8), the attempts under step control.
     map_cloud=True: the accumulated map (mapCloudPtr) is kept on the device (``closer.map``)
     and its 0.4 m VoxelGrid is published on /sum_map_cloud_res3 for every keyframe whose pair
     count numFrame (first pair = 1) is a multiple of 5 (publishResult :387-397)."""
 
     def __init__(self, publish, device=None, frontend: Frontend | None = None,
                  tum_path: str | None = None, optimize: bool = False, map_cloud: bool = False,
-                 map_robust=None):
-        from .loop import LoopCloser, get_translation_and_euler_angles  # noqa: F401
+                 map_robust=None, map_lm=None, map_iters: int | None = None):
+        from .loop import LoopCloser, get_translation_and_euler_angles, pgo_params  # noqa: F401
         self.publish = publish
         self.fe = frontend or Frontend(64, device=device)
         if map_robust is not None and not optimize:
             raise ValueError("map_robust is a loss of the pose-graph solve: it needs optimize=True")
+        if map_lm is not None and not optimize:
+            raise ValueError("map_lm is the step control of the pose-graph solve: it needs optimize=True")
+        if map_iters is not None and not optimize:
+            raise ValueError("map_iters is the iteration limit of the pose-graph solve: it needs optimize=True")
+        if map_iters is not None and int(map_iters) <= 0:
+            raise ValueError("map_iters must be positive")
         kw = dict(optimize=True) if optimize else {}
+        if map_lm is not None:
+            kw["lm"] = map_lm
+        if map_iters is not None:
+            kw["pgo"] = pgo_params(max_iter=int(map_iters))
         if map_cloud:
             kw["map_cloud"] = True
         if map_robust is not None:
@@ -367,7 +379,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
                  solver: str = "ceres_lm", max_iter: int | None = None, seed: int | None = None,
                  rate_hz: float = 10.0, launch: str = "onlyPC", map_tum_path: str | None = None,
                  truncate_results: bool = False, map_optimize: bool = False, map_cloud: bool = False,
-                 weights=None, n_points: int = 8192, map_robust=None):
+                 weights=None, n_points: int = 8192, map_robust=None, map_lm=None,
+                 map_iters: int | None = None):
     """Replay a DATASET_PATH directory through the node graph of launch/run_<launch>.launch:
       onlyPC: PointCloudOdometry_onlyPC -> frameFeature -> lidarOdometry_onlyPC (registration)
       noSeg:  PointCloudOdometry_noSeg (GMM mask + Kabsch -> /frame_odom1) -> frameFeature ->
@@ -380,7 +393,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
               and the GMM take `seed` (default 1234)
     plus mapOptmization when `map_tum_path` is given (map_optimize: with the GPU pose-graph
     optimisation of its loop closures; map_robust: an ssf.loop.pgo_robust loss on their loop
-    edges, which needs map_optimize).  Stamps are synthetic and monotone (frame k
+    edges, map_lm: an ssf.loop.pgo_lm step control for those solves, map_iters: their max_iter;
+    all three need map_optimize).  Stamps are synthetic and monotone (frame k
     at k / rate_hz; the reference uses wall-clock ros::Time::now()).  The /frame_odom2 poses are
     appended to `tum_path` as TUM lines (like the reference, an existing file is extended unless
     truncate_results=True).
@@ -395,6 +409,12 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
         raise ValueError("map_cloud needs mapOptmization in the graph: pass map_tum_path")
     if map_robust is not None and not map_optimize:
         raise ValueError("map_robust is a loss of the pose-graph solve: it needs map_optimize")
+    if map_lm is not None and not map_optimize:
+        raise ValueError("map_lm is the step control of the pose-graph solve: it needs map_optimize")
+    if map_iters is not None and not map_optimize:
+        raise ValueError("map_iters is the iteration limit of the pose-graph solve: it needs map_optimize")
+    if map_iters is not None and int(map_iters) <= 0:
+        raise ValueError("map_iters must be positive")
     src_mode, odo_kind, keys = LAUNCH_GRAPHS[launch][:3]
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     bus = Bus()
@@ -440,6 +460,10 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
             mkw["map_cloud"] = True
         if map_robust is not None:
             mkw["map_robust"] = map_robust
+        if map_lm is not None:
+            mkw["map_lm"] = map_lm
+        if map_iters is not None:
+            mkw["map_iters"] = map_iters
         mo = MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None, **mkw)
         bus.subscribe("/plane_frame_cloud2", mo.on_plane_cloud)
         bus.subscribe("/frame_odom2", mo.on_odom)

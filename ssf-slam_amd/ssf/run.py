@@ -34,6 +34,13 @@ def main(argv=None):
                     help="with --map-optimize: a robust loss on the loop edges of the pose graph, "
                          "huber, cauchy or geman_mcclure (or none), K its threshold (default 1.345 / "
                          "0.1 / 1.0)")
+    ap.add_argument("--map-lm", nargs="?", const=True, default=None, metavar="RADIUS0",
+                    help="with --map-optimize: Levenberg-Marquardt step control for the pose-graph solves "
+                         "(no step that raises the cost is taken); RADIUS0 the initial trust-region radius "
+                         "(default 1e4)")
+    ap.add_argument("--map-iters", type=int, default=None, metavar="N",
+                    help="with --map-optimize: the iteration limit of the pose-graph solves (default 8); "
+                         "with --map-lm it bounds the attempts")
     ap.add_argument("--map-cloud", default=None, metavar="FILE.npy",
                     help="with --map-tum: keep the accumulated map cloud on the GPU, publish its 0.4 m "
                          "VoxelGrid on /sum_map_cloud_res3 and save the final one as float32 [M, 4]")
@@ -62,6 +69,20 @@ def main(argv=None):
             kw["map_robust"] = parse_robust(a.map_robust)
         except ValueError as e:
             ap.error(f"--map-robust: {e}")
+    if a.map_lm is not None:
+        if not a.map_optimize:
+            ap.error("--map-lm needs --map-optimize")
+        from .loop import parse_lm
+        try:
+            kw["map_lm"] = parse_lm(a.map_lm)
+        except ValueError as e:
+            ap.error(f"--map-lm: {e}")
+    if a.map_iters is not None:
+        if not a.map_optimize:
+            ap.error("--map-iters needs --map-optimize")
+        if a.map_iters <= 0:
+            ap.error("--map-iters: must be positive")
+        kw["map_iters"] = a.map_iters
     torch.cuda.set_device(a.device)
     from .nodes import ASF_LAUNCHES
     if a.launch in ASF_LAUNCHES:
@@ -78,6 +99,11 @@ def main(argv=None):
                  {k: opt[k] for k in ("status_name", "iterations", "cost0", "cost", "loops")}}
         if a.map_robust is not None and opt is not None:
             extra["map_optimize"]["robust"] = a.map_robust
+        if a.map_lm is not None and opt is not None:
+            extra["map_optimize"]["lm"] = kw["map_lm"].radius0
+            extra["map_optimize"].update(accepted=opt["accepted"], radius=opt["radius"])
+        if a.map_iters is not None and opt is not None:
+            extra["map_optimize"]["iters"] = a.map_iters
     if a.map_cloud:
         import numpy as np
         with open(a.map_cloud, "wb") as f:           # the name as given (np.save appends .npy to a path)

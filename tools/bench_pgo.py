@@ -12,7 +12,12 @@ device-to-device copy outside the timed region).  Writes profiles/pgo_bench.json
 --robust KIND[:K] times ssf_pose_graph_batch_robust with that loss on the loop edges (and the
 per-edge output) against the plain call instead: the `batch` and `long` lines, plain and robust
 alternated in one process, three runs of each (every run: warm-up, then the median of --runs
-samples).  Writes profiles/pgo_robust_bench.json."""
+samples).  Writes profiles/pgo_robust_bench.json.
+
+--lm [RADIUS0] times ssf_pose_graph_batch_lm (step control, no loss, RADIUS0 default 1e4) against
+the plain call by the same protocol, and reports the time of an attempt over the time of a plain
+iteration (each call's median over the largest iteration / attempt count of its graphs).  Writes
+profiles/pgo_lm_bench.json."""
 import argparse
 import ctypes as C
 import json
@@ -73,6 +78,8 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/pgo_bench.json (pgo_robust_bench.json with --robust)")
     ap.add_argument("--robust", default=None, metavar="KIND[:K]",
                     help="time this loss (huber, cauchy, geman_mcclure; K default 1.345 / 0.1 / 1.0) against the plain call")
+    ap.add_argument("--lm", nargs="?", const="1e4", default=None, metavar="RADIUS0",
+                    help="time the step control (initial radius RADIUS0, default 1e4) against the plain call")
     ap.add_argument("--only", default="", help="comma-separated line names (default: all)")
     a = ap.parse_args()
     only = [n for n in a.only.split(",") if n]
@@ -80,8 +87,10 @@ def main():
         ap.error(f"--only: unknown line in {only}")
     if a.runs < 20:
         ap.error("--runs must be at least 20")
-    if a.robust and only:
-        ap.error("--robust times the batch and long lines: no --only")
+    if (a.robust or a.lm) and only:
+        ap.error("--robust and --lm time the batch and long lines: no --only")
+    if a.robust and a.lm:
+        ap.error("--robust or --lm, not both")
     import torch
     from ssf import Frontend, _abi
     robust = None
@@ -92,7 +101,16 @@ def main():
         except ValueError as e:
             ap.error(f"--robust: {e}")
         only = ["batch", "long"]
-    a.out = a.out or os.path.join(REPO, "profiles", "pgo_robust_bench.json" if robust else "pgo_bench.json")
+    lm = None
+    if a.lm:
+        from ssf.loop import parse_lm
+        try:
+            lm = parse_lm(a.lm)
+        except ValueError as e:
+            ap.error(f"--lm: {e}")
+        only = ["batch", "long"]
+    a.out = a.out or os.path.join(REPO, "profiles", "pgo_robust_bench.json" if robust else
+                                  "pgo_lm_bench.json" if lm else "pgo_bench.json")
     from ssf.frontend import _ptr, _stream
     dev = torch.device("cuda", 0)
     fe = Frontend(64, device=dev)
@@ -117,6 +135,12 @@ def main():
         eout = torch.zeros(G * (K - 1 + nl), _abi.PGO_EDGE_OUT_STRIDE, dtype=torch.float64, device=dev)
 
         def call(rb):
+            if rb is lm and lm is not None:
+                fe._check(L.ssf_pose_graph_batch_lm(
+                    fe._h, _stream(dev), G, _ptr(pose), _ptr(d_noff), C.c_void_p(h_noff.data_ptr()), _ptr(ij),
+                    _ptr(meas), _ptr(var), _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(prior), _ptr(pvar),
+                    C.byref(prm), _ptr(stats), None, None, None, C.byref(lm), None), "ssf_pose_graph_batch_lm")
+                return
             args = (fe._h, _stream(dev), G, _ptr(pose), _ptr(d_noff), C.c_void_p(h_noff.data_ptr()), _ptr(ij),
                     _ptr(meas), _ptr(var), _ptr(d_eoff), C.c_void_p(h_eoff.data_ptr()), _ptr(prior), _ptr(pvar),
                     C.byref(prm), _ptr(stats), None)
@@ -142,6 +166,8 @@ def main():
                        max_ms=float(np.max(ms)), iterations=sorted(set(int(v) for v in st[:, 1])),
                        status=[_abi.PGO_STATUS[s] for s in status], cost0=float(st[0, 2]), cost=float(st[0, 3]),
                        max_iter=prm.max_iter, func_tol=prm.func_tol)
+            if rb is lm and lm is not None:
+                row["accepted"] = sorted(set(int(v) for v in st[:, _abi.PGO_OUT["ACCEPTED"]]))
             if any(s not in (_abi.PGO_OK, _abi.PGO_CONVERGED) for s in status):
                 raise SystemExit(f"{sh['name']}: a graph failed: {row['status']}")
             return row
@@ -158,6 +184,21 @@ def main():
                                 robust_over_plain=float(np.median(med(a.robust)) / np.median(med("plain")))))
             print(json.dumps(summary[-1]), flush=True)
             continue
+        if lm is not None:                           # plain and step control in turn, three runs of each
+            for rep in range(3):
+                for label, how in (("plain", None), ("lm", lm)):
+                    row = dict(sample(how), solver=label, rep=rep)
+                    print(json.dumps(row), flush=True)
+                    results.append(row)
+            rows = lambda label: [r for r in results if r["name"] == sh["name"] and r["solver"] == label]  # noqa: E731
+            per = lambda label: float(np.median([r["median_ms"] / max(r["iterations"]) for r in rows(label)]))  # noqa: E731
+            summary.append(dict(name=sh["name"], plain_median_ms=[r["median_ms"] for r in rows("plain")],
+                                lm_median_ms=[r["median_ms"] for r in rows("lm")],
+                                plain_iterations=rows("plain")[0]["iterations"], lm_attempts=rows("lm")[0]["iterations"],
+                                lm_accepted=rows("lm")[0]["accepted"], plain_ms_per_iteration=per("plain"),
+                                lm_ms_per_attempt=per("lm"), attempt_over_iteration=per("lm") / per("plain")))
+            print(json.dumps(summary[-1]), flush=True)
+            continue
         row = sample(None)
         ref = [r for r in results if r["name"] == sh.get("ref")]
         if ref:                                      # against the L = 32 line of the same G and K
@@ -169,6 +210,10 @@ def main():
                shapes=results)
     if robust is not None:
         out.update(robust=a.robust, k=robust.k, protocol="plain and robust alternated, three runs of each", summary=summary)
+    if lm is not None:
+        out.update(lm=dict(radius0=lm.radius0, min_relative_decrease=lm.min_relative_decrease,
+                           max_radius=lm.max_radius, min_radius=lm.min_radius),
+                   protocol="plain and step control alternated, three runs of each", summary=summary)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
