@@ -21,6 +21,7 @@ SRC_DEPS = {"mask_pose_f64.hip": ["mask_pose.hip"]}
 HEADERS = ["ssf_device.hpp", "ssf_internal.hpp", "feat_common.hpp", "reg_knn.hpp", "reg_strips.hpp", "svd3.hpp", "mlp_tile.hpp",
            "mask_common.hpp", "mask_exchange.hpp", "mask_gmm.hpp", "mask_kabsch.hpp", "mask_seed.hpp", "mask_lloyd.hpp",
            "mask_em.hpp", "mask_final.hpp",
+           "pgo_common.hpp", "pgo_linearise.hpp", "pgo_tridiag.hpp", "pgo_capacitance.hpp", "pgo_step.hpp",
            os.path.join("..", "..", "include", "ssf_frontend.h"),
            os.path.join("..", "..", "include", "ssf_pointnet2.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

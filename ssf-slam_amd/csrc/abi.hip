@@ -1105,7 +1105,54 @@ static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, doub
                                 const int32_t* h_edge_off, const double* d_prior_pose,
                                 const double* d_prior_var, const ssf_pgo_params* prm,
                                 double* d_stats, double* d_cost_log, bool robust, int rkind, double rk,
-                                double* d_edge_out, const ssf_pgo_lm* lm, double* d_lm_log);
+                                double* d_edge_out, const ssf_pgo_lm* lm, double* d_lm_log) {
+    if (!c) return SSF_E_ARG;
+    if (n_graphs < 0 || !prm || prm->max_iter < 0 || prm->max_iter > SSF_PGO_MAX_ITER ||
+        !(prm->func_tol >= 0.0) ||
+        (n_graphs > 0 && (!d_pose || !d_node_off || !h_node_off || !d_edge_ij || !d_edge_meas || !d_edge_var ||
+                          !d_edge_off || !h_edge_off || !d_prior_pose || !d_prior_var || !d_stats)))
+        return fail(c, SSF_E_ARG, "pose_graph_batch: bad arguments");
+    if (n_graphs == 0) return SSF_OK;
+    if (h_node_off[0] != 0 || h_edge_off[0] != 0)
+        return fail(c, SSF_E_ARG, "pose_graph_batch: offsets must start at 0");
+    for (int g = 0; g < n_graphs; ++g)
+        if (h_node_off[g + 1] < h_node_off[g] || h_edge_off[g + 1] < h_edge_off[g])
+            return fail(c, SSF_E_ARG, "pose_graph_batch: offsets not monotone");
+    c->pgo_h.resize((size_t)n_graphs);
+    size_t total = 0;
+    bool any_narrow = false, any_wide = false;
+    for (int g = 0; g < n_graphs; ++g) {
+        ssf::PgoGraph& G = c->pgo_h[(size_t)g];
+        G.node0 = h_node_off[g]; G.K = h_node_off[g + 1] - h_node_off[g];
+        G.edge0 = h_edge_off[g]; G.E = h_edge_off[g + 1] - h_edge_off[g];
+        G.lcap = std::min(std::max(G.E - (G.K - 1), 0), SSF_PGO_MAX_LOOPS);
+        G.wide = ssf::pgo_graph_wide(G.K, G.E);
+        (G.wide ? any_wide : any_narrow) = true;
+        G.scratch_off = (int64_t)total;
+        total += ssf::pgo_graph_doubles(G.K, G.E, G.lcap, G.wide != 0, lm != nullptr);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(c, stream);
+    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    SSF_TRY_HIP(c, c->pgo_desc.ensure(sizeof(ssf::PgoGraph) * (size_t)n_graphs), "alloc pose-graph descriptors");
+    SSF_TRY_HIP(c, c->pgo_scratch.ensure(sizeof(double) * total), "alloc pose-graph scratch");
+    SSF_TRY_HIP(c, hipMemcpyAsync(c->pgo_desc.p, c->pgo_h.data(), sizeof(ssf::PgoGraph) * (size_t)n_graphs,
+                                  hipMemcpyHostToDevice, s), "H2D pose-graph descriptors");
+    ssf::PgoArgs a{};
+    a.desc = c->pgo_desc.as<ssf::PgoGraph>();
+    a.pose = d_pose; a.node_off = d_node_off; a.edge_ij = d_edge_ij; a.edge_meas = d_edge_meas;
+    a.edge_var = d_edge_var; a.edge_off = d_edge_off; a.prior_pose = d_prior_pose; a.prior_var = d_prior_var;
+    a.max_iter = prm->max_iter; a.func_tol = prm->func_tol;
+    a.scratch = c->pgo_scratch.as<double>();
+    a.stats = d_stats; a.cost_log = d_cost_log;
+    a.rkind = rkind; a.rk = rk; a.edge_out = d_edge_out;
+    if (lm) a.lm = *lm;
+    a.lm_log = d_lm_log;
+    a.robust = robust; a.has_lm = lm != nullptr;
+    const hipError_t e = ssf::launch_pose_graph(s, n_graphs, any_narrow, any_wide, a);
+    if (e != hipSuccess) return hip_fail(c, e, "pose_graph launch");
+    return SSF_OK;
+}
 
 int32_t ssf_pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
                              const int32_t* d_node_off, const int32_t* h_node_off,
@@ -1170,66 +1217,6 @@ int32_t ssf_pose_graph_batch_lm(ssf_ctx* c, void* stream, int32_t n_graphs, doub
                             d_edge_var, d_edge_off, h_edge_off, d_prior_pose, d_prior_var, prm, d_stats,
                             d_cost_log, !plain, rkind, rkind != SSF_PGO_ROBUST_NONE ? robust->k : 0.0,
                             d_edge_out, lm, d_lm_log);
-}
-
-static int32_t pose_graph_batch(ssf_ctx* c, void* stream, int32_t n_graphs, double* d_pose,
-                                const int32_t* d_node_off, const int32_t* h_node_off,
-                                const int32_t* d_edge_ij, const double* d_edge_meas,
-                                const double* d_edge_var, const int32_t* d_edge_off,
-                                const int32_t* h_edge_off, const double* d_prior_pose,
-                                const double* d_prior_var, const ssf_pgo_params* prm,
-                                double* d_stats, double* d_cost_log, bool robust, int rkind, double rk,
-                                double* d_edge_out, const ssf_pgo_lm* lm, double* d_lm_log) {
-    if (!c) return SSF_E_ARG;
-    if (n_graphs < 0 || !prm || prm->max_iter < 0 || prm->max_iter > SSF_PGO_MAX_ITER ||
-        !(prm->func_tol >= 0.0) ||
-        (n_graphs > 0 && (!d_pose || !d_node_off || !h_node_off || !d_edge_ij || !d_edge_meas || !d_edge_var ||
-                          !d_edge_off || !h_edge_off || !d_prior_pose || !d_prior_var || !d_stats)))
-        return fail(c, SSF_E_ARG, "pose_graph_batch: bad arguments");
-    if (n_graphs == 0) return SSF_OK;
-    if (h_node_off[0] != 0 || h_edge_off[0] != 0)
-        return fail(c, SSF_E_ARG, "pose_graph_batch: offsets must start at 0");
-    for (int g = 0; g < n_graphs; ++g)
-        if (h_node_off[g + 1] < h_node_off[g] || h_edge_off[g + 1] < h_edge_off[g])
-            return fail(c, SSF_E_ARG, "pose_graph_batch: offsets not monotone");
-    c->pgo_h.resize((size_t)n_graphs);
-    size_t total = 0;
-    bool any_narrow = false, any_wide = false;
-    for (int g = 0; g < n_graphs; ++g) {
-        ssf::PgoGraph& G = c->pgo_h[(size_t)g];
-        G.node0 = h_node_off[g]; G.K = h_node_off[g + 1] - h_node_off[g];
-        G.edge0 = h_edge_off[g]; G.E = h_edge_off[g + 1] - h_edge_off[g];
-        G.lcap = std::min(std::max(G.E - (G.K - 1), 0), SSF_PGO_MAX_LOOPS);
-        G.wide = ssf::pgo_graph_wide(G.K, G.E);
-        (G.wide ? any_wide : any_narrow) = true;
-        G.scratch_off = (int64_t)total;
-        total += ssf::pgo_graph_doubles(G.K, G.E, G.lcap, G.wide != 0, lm != nullptr);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(c, stream);
-    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
-    SSF_TRY_HIP(c, c->pgo_desc.ensure(sizeof(ssf::PgoGraph) * (size_t)n_graphs), "alloc pose-graph descriptors");
-    SSF_TRY_HIP(c, c->pgo_scratch.ensure(sizeof(double) * total), "alloc pose-graph scratch");
-    SSF_TRY_HIP(c, hipMemcpyAsync(c->pgo_desc.p, c->pgo_h.data(), sizeof(ssf::PgoGraph) * (size_t)n_graphs,
-                                  hipMemcpyHostToDevice, s), "H2D pose-graph descriptors");
-    hipError_t e;
-    if (lm)
-        e = ssf::launch_pose_graph_lm(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose,
-                                      d_node_off, d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
-                                      d_prior_var, prm->max_iter, prm->func_tol, c->pgo_scratch.as<double>(),
-                                      d_stats, d_cost_log, rkind, rk, d_edge_out, *lm, d_lm_log);
-    else if (robust)
-        e = ssf::launch_pose_graph_robust(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose,
-                                          d_node_off, d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
-                                          d_prior_var, prm->max_iter, prm->func_tol,
-                                          c->pgo_scratch.as<double>(), d_stats, d_cost_log, rkind, rk, d_edge_out);
-    else
-        e = ssf::launch_pose_graph(s, n_graphs, any_narrow, any_wide, c->pgo_desc.as<ssf::PgoGraph>(), d_pose, d_node_off,
-                                   d_edge_ij, d_edge_meas, d_edge_var, d_edge_off, d_prior_pose,
-                                   d_prior_var, prm->max_iter, prm->func_tol,
-                                   c->pgo_scratch.as<double>(), d_stats, d_cost_log);
-    if (e != hipSuccess) return hip_fail(c, e, "pose_graph launch");
-    return SSF_OK;
 }
 
 }  // extern "C"

@@ -322,26 +322,34 @@ struct PgoGraph {             // one per graph, built on the host from the host 
 };
 bool pgo_graph_wide(int K, int E);      // more than 32 edges beyond K - 1: it may hold more than 32 loops
 size_t pgo_graph_doubles(int K, int E, int lcap, bool wide, bool lm);   // lm: with the trial buffers
-hipError_t launch_pose_graph(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
-                             const PgoGraph* desc, double* pose,
-                             const int32_t* node_off, const int32_t* edge_ij, const double* edge_meas,
-                             const double* edge_var, const int32_t* edge_off, const double* prior_pose,
-                             const double* prior_var, int max_iter, double func_tol, double* scratch,
-                             double* stats, double* cost_log);
-// the kernels with a loss (ssf_pgo_robust: rkind, rk) on the loop edges; edge_out is nullable
-hipError_t launch_pose_graph_robust(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
-                                    const PgoGraph* desc, double* pose, const int32_t* node_off,
-                                    const int32_t* edge_ij, const double* edge_meas, const double* edge_var,
-                                    const int32_t* edge_off, const double* prior_pose, const double* prior_var,
-                                    int max_iter, double func_tol, double* scratch, double* stats,
-                                    double* cost_log, int rkind, double rk, double* edge_out);
-// the loss kernels with step control (ssf_pgo_lm); lm_log is nullable
-hipError_t launch_pose_graph_lm(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide,
-                                const PgoGraph* desc, double* pose, const int32_t* node_off,
-                                const int32_t* edge_ij, const double* edge_meas, const double* edge_var,
-                                const int32_t* edge_off, const double* prior_pose, const double* prior_var,
-                                int max_iter, double func_tol, double* scratch, double* stats,
-                                double* cost_log, int rkind, double rk, double* edge_out, const ssf_pgo_lm& lm,
-                                double* lm_log);
+// The arguments of the pose-graph kernels, passed to them by value; value-initialise, then set
+// (device pointers unless noted).  The first 14 are every kernel's.
+struct PgoArgs {
+    const PgoGraph* desc;
+    double* pose;
+    const int32_t* node_off;
+    const int32_t* edge_ij;
+    const double* edge_meas;
+    const double* edge_var;
+    const int32_t* edge_off;
+    const double* prior_pose;
+    const double* prior_var;
+    int max_iter;
+    double func_tol;
+    double* scratch;          // sized by pgo_graph_doubles, with lm = has_lm
+    double* stats;
+    double* cost_log;         // nullable
+    // the kernels with a loss (ssf_pgo_robust: rkind, rk) on the loop edges
+    int rkind;
+    double rk;
+    double* edge_out;         // nullable
+    // the loss kernels with step control
+    ssf_pgo_lm lm;
+    double* lm_log;           // nullable
+    // which kernel pair (host only): has_lm the step-control kernels, else robust the loss
+    // kernels, else the plain ones
+    bool robust, has_lm;
+};
+hipError_t launch_pose_graph(hipStream_t s, int n_graphs, bool any_narrow, bool any_wide, const PgoArgs& a);
 
 }  // namespace ssf

@@ -23,7 +23,11 @@ def test_loop_cap_constants_agree():
     assert f"#define SSF_PGO_MAX_LOOPS {_abi.PGO_MAX_LOOPS}" in hdr
     assert f"#define SSF_PGO_OUT_STRIDE {_abi.PGO_OUT_STRIDE}" in hdr
     assert f"#define SSF_PGO_MAX_ITER {_abi.PGO_MAX_ITER}" in hdr
-    src = open(os.path.join(ROOT, "ssf-slam_amd", "csrc", "pose_graph.hip")).read()
+    csrc = os.path.join(ROOT, "ssf-slam_amd", "csrc")           # the kernel source: pose_graph.hip and its stage headers
+    src = open(os.path.join(csrc, "pose_graph.hip")).read()
+    stages = re.findall(r'#include "(pgo_\w+\.hpp)"', src)
+    assert stages
+    src += "".join(open(os.path.join(csrc, h)).read() for h in stages)
     m = re.search(r"constexpr int kPgoNarrowLoops = (\d+);", src)
     assert m and int(m.group(1)) == W.NARROW_LOOPS == 32
     assert "L > SSF_PGO_MAX_LOOPS" in src                # the kernel's cap is the header's
