@@ -11,7 +11,9 @@ vectors generated from the reference's own scripts/PointCloudOdometry_noSeg.py; 
 binary (ROS/PCL/Eigen/Ceres are absent, so it cannot be built) and is pinned only by
 known-answer tests.  The 3x3 algebra both halves end in (svd3, kabsch, quat_from_R, the Umeyama
 and convergence block of icp) is pinned to an independent numpy yardstick
-(tests/rigid_reference.py, tests/test_rigid_host.py).  See oracle/ssf_oracle.h and DESIGN.md.
+(tests/rigid_reference.py, tests/test_rigid_host.py), and so are the feature stage (bin_rings,
+curvature, select, extract_planes) and voxel_grid, bit for bit (tests/feature_reference.py,
+tests/test_feature_host.py).  See oracle/ssf_oracle.h and DESIGN.md.
 """
 from __future__ import annotations
 
