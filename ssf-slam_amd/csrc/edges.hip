@@ -161,7 +161,13 @@ __global__ __launch_bounds__(kEdgeAssocThreads) void k_edge_associate(
     CorrRec rec;
     rec.po[0] = pc.x; rec.po[1] = pc.y; rec.po[2] = pc.z;
     rec.valid = (bi >= 0 && line_valid[lo + bi]) ? 1.0f : 0.0f;
-    const float* L = line + 6 * (lo + (bi >= 0 ? bi : 0));
+    // an empty last frame (bi < 0) has no row of its own: lo may be the table's row count
+    float L[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (bi >= 0) {
+        const float* row = line + 6 * (lo + bi);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) L[j] = row[j];
+    }
     rec.pa[0] = L[0]; rec.pa[1] = L[1]; rec.pa[2] = L[2]; rec.pad0 = 0.f;
     rec.n[0] = L[3]; rec.n[1] = L[4]; rec.n[2] = L[5]; rec.pad1 = 0.f;
     corr[co + i] = rec;

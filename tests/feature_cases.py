@@ -249,8 +249,33 @@ def cases(n_rows):
     return tuple(out)
 
 
+# ------------------------------------------------------------------------------- edge rows
+# Row cases of the project's edge selection (tests/edge_cases.py runs them after cases(); they
+# are not part of cases(), whose plane tests they would only lengthen).
+LONG_ROW = {64: 31, 16: 9}
+LONG_ROW_POINTS = 4200                           # more than 4097: a row over three 2048-point chunks
+EDGE_MIN_ROW = {64: 20, 16: 7}                   # the 2049-point row of "dense"
+
+
+@functools.lru_cache(maxsize=None)
+def edge_rows(n_rows):
+    """long_row: one in-range row of 4200 noisy points (at edge_span 1 every candidate word of
+    it is walked bit by bit) between two short rows.  flat: smooth arcs only -- no curvature
+    exceeds any edge_min the tests use, the frame's edge list is empty."""
+    rng = np.random.default_rng(500 + n_rows)
+    r = LONG_ROW[n_rows]
+    a = _case("long_row", n_rows, [(r - 1, noisy_row(rng, n_rows, r - 1, 70)),
+                                   (r, noisy_row(rng, n_rows, r, LONG_ROW_POINTS, az0=0.2)),
+                                   (r + 1, noisy_row(rng, n_rows, r + 1, 33))])
+    b = _case("flat", n_rows, [(q, flat_row(n_rows, q, 90)) for q in range(n_rows)], equal_rows=True)
+    for cs in (a, b):
+        cs.pts.setflags(write=False)
+        cs.run.setflags(write=False)
+    return (a, b)
+
+
 # ------------------------------------------------------------------------------- layouts
-LAYOUTS = ("rowmajor", "descending", "interleaved", "shuffled", "masked", "stride4")
+LAYOUTS =("rowmajor", "descending", "interleaved", "shuffled", "masked", "stride4")
 
 
 def _pos_in_run(run):

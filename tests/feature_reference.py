@@ -6,9 +6,14 @@ from the kernels, and it imports nothing of either.  The source evaluates float 
 written order; a numpy float32 element-wise operation rounds once, as each C operation does, so a
 row is evaluated with shifted float32 arrays and the results are comparable bit for bit.
 
+The project's own edge selection (select_edges, extract_features) has no reference source: it is
+written from the definition in the header comment of oracle/edge_oracle.c, and reuses this
+file's ring ids, binning and curvature.
+
 Every rule is also reachable as a deliberately WRONG variant through a keyword (VARIANTS at the
-end).  They exist for one purpose: tests/test_feature_host.py shows that for each of them some
-case of tests/feature_cases.py changes its output, so the cases do reach the rule.
+end).  They exist for one purpose: tests/test_feature_host.py (tests/test_edge_host.py for the
+edge rules) shows that for each of them some case of tests/feature_cases.py changes its output,
+so the cases do reach the rule.
 """
 import numpy as np
 
@@ -167,6 +172,66 @@ def extract_planes(pts, n_rows, **wrong):
     return dict(ids=ids, margin=margin, rx=rx, off=off, src=src, cv=cv, planes=planes, sel=sel)
 
 
+# ------------------------------------------------------------------------------- edges
+# The project's own edge selection (the reference has none), from the definition in the header
+# comment of oracle/edge_oracle.c -- not from its functions and not from the kernels: per row in
+# [rowStart, N - rowEnd), greedy in index order, a point is emitted when j >= jstart and
+# curvature > edge_min, and then jstart = j + edge_span.  The comparison is strict and in
+# float32 (inf passes, NaN does not); the walk has its own jstart, apart from the plane walk's.
+def select_edges(rx, cv, off, n_rows, edge_min, edge_span, row_lo=0, row_hi=0, span_delta=0, ge=False,
+                 shared_jstart=False):
+    """-> (edge list [m, 4], ring positions [m]).
+    WRONG variants: ge (>= for >), span_delta, row_lo / row_hi, shared_jstart (ONE jstart for
+    the plane walk and the edge walk of a row: either kind of pick pushes it on by its own span)."""
+    pr = _profile(n_rows)
+    rx = np.asarray(rx, F32)
+    cv = np.asarray(cv, F32)
+    em, span = F32(edge_min), int(edge_span) + span_delta
+    pm, pspan = F32(pr["plane_min"]), pr["span"]
+    r0, r1 = _row_range(n_rows, row_lo, row_hi)
+    sel = []
+    for r in range(r0, r1):
+        a, b = int(off[r]), int(off[r + 1])
+        v = cv[a:b]
+        with np.errstate(invalid="ignore"):
+            is_edge = (v >= em) if ge else (v > em)                      # NaN: never
+            is_plane = v < pm
+        jstart = 0
+        if shared_jstart:
+            for j in np.nonzero(is_edge | is_plane)[0].tolist():
+                if j >= jstart:
+                    if is_plane[j]:
+                        jstart = j + pspan
+                    else:
+                        sel.append(a + j)
+                        jstart = j + span
+            continue
+        for j in np.nonzero(is_edge)[0].tolist():
+            if j >= jstart:
+                sel.append(a + j)
+                jstart = j + span
+    sel = np.array(sel, np.int64)
+    return rx[sel], sel
+
+
+EDGE_SELECT_KEYS = ("row_lo", "row_hi", "span_delta", "ge", "shared_jstart")
+
+
+def extract_features(pts, n_rows, edge_min, edge_span, **wrong):
+    """extract_planes() plus the edge list: -> its dict with edges [m, 4] and esel [m] added.
+    Keywords are select_edges' wrong variants; the planes are always the right ones.  A wrong
+    row range is the curvature's too (outside the right one every value is 0 and nothing could
+    be selected): the edge walk then sees the curvature of the rows it wrongly includes."""
+    unknown = set(wrong) - set(EDGE_SELECT_KEYS)
+    if unknown:
+        raise TypeError(f"unknown variant keyword {sorted(unknown)}")
+    y = dict(extract_planes(pts, n_rows))
+    rows = {k: wrong[k] for k in ("row_lo", "row_hi") if k in wrong}
+    cv = curvature(y["rx"], y["off"], n_rows, **rows) if rows else y["cv"]
+    y["edges"], y["esel"] = select_edges(y["rx"], cv, y["off"], n_rows, edge_min, edge_span, **wrong)
+    return y
+
+
 # ------------------------------------------------------------------------------- VoxelGrid
 def voxel_passthrough(xyzi, leaf):
     """PCL's overflow guard: (int64((max - min) * inv) + 1) over the three axes > INT32_MAX"""
@@ -219,6 +284,12 @@ FEATURE_VARIANTS = {
     "stencil range [4, size-4)": dict(edge=4), "stencil range [6, size-6)": dict(edge=6),
     "intensity summed in float32": dict(intensity_f32=True),
     "unstable partition": dict(unstable=True),
+}
+EDGE_VARIANTS = {
+    ">= for >": dict(ge=True), "jstart = j + span + 1": dict(span_delta=1), "jstart = j + span - 1": dict(span_delta=-1),
+    "one jstart shared with the plane walk": dict(shared_jstart=True),
+    "row range starts one early": dict(row_lo=-1), "row range starts one late": dict(row_lo=1),
+    "row range ends one early": dict(row_hi=-1), "row range ends one late": dict(row_hi=1),
 }
 VOXEL_VARIANTS = {"truncation for floor": dict(truncate=True),
                   "sums in sorted-coordinate order": dict(sorted_sums=True)}

@@ -246,6 +246,51 @@ def g_edge(n_pl, n_e, base):
     return g
 
 
+EDGE_LDS_CAP = 8192            # kEdgeLdsMax of edges.hip: a larger last edge cloud is read from global memory
+
+
+def edge_lds_cap():
+    """kEdgeLdsMax as edges.hip states it, so a changed cap cannot leave the fallback untested
+    without a test saying so"""
+    import os
+    import re
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ssf-slam_amd", "csrc", "edges.hip")
+    return int(re.search(r"constexpr int kEdgeLdsMax = (\d+);", open(src).read()).group(1))
+
+
+def g_edge_big_last(rng, solver):
+    """edge_both with a last edge cloud of more than EDGE_LDS_CAP points: k_edge_associate's
+    global-memory fallback (ml > lds_cap).  The extra points are invalid filler kilometres away on a
+    line of its own, half of it before the real points and half after, so the real ones sit at
+    indices from 4100 on and no filler point is ever one of a query's two nearest (the gap that
+    admit() requires is the real points')."""
+    cs = g_edge(200, 60, "edge_big_last")(rng, solver)
+    last_e, line, lvalid, curr_e = cs.edges
+    n_fill = EDGE_LDS_CAP + 8
+    fill = last_e[:, :3].astype(np.float64).mean(0) + 3000.0 + 3.0 * np.arange(n_fill)[:, None] * np.array([1.0, -0.4, 0.25])
+    h = n_fill // 2
+    z = lambda k, w: np.zeros((k, w), np.float32)                                               # noqa: E731
+    cs.edges = (_xyzi(np.concatenate([fill[:h], last_e[:, :3], fill[h:]])),
+                np.concatenate([z(h, 6), line, z(n_fill - h, 6)]),
+                np.r_[np.zeros(h, np.uint8), lvalid, np.zeros(n_fill - h, np.uint8)], curr_e)
+    assert len(cs.edges[0]) > EDGE_LDS_CAP
+    return cs
+
+
+def g_edge_pair(empty_last):
+    """A launch of its own (max_iter one above its solver's, so the family test batches the two
+    together and apart from the rest): edge_pair_first is edge_both again; edge_pair_empty_last,
+    the batch's LAST pair, has an empty last edge cloud and 60 current edge points -- no edge
+    record is valid, and its last-frame offset is the line table's row count."""
+    def g(rng, solver):
+        cs = g_edge(200, 60, "edge_pair_empty_last" if empty_last else "edge_pair_first")(rng, solver)
+        cs.max_iter = ITERS[solver] + 1
+        if empty_last:
+            cs.edges = (np.zeros((0, 4), np.float32), np.zeros((0, 6), np.float32), np.zeros(0, np.uint8), cs.edges[3])
+        return cs
+    return g
+
+
 def _has(status):
     return lambda y: status in y["sol"]["log"][:, 8]
 
@@ -277,7 +322,8 @@ GEN = dict(clean=g_clean, outliers=g_outliers, knee=g_knee, at_solution=g_at_sol
            norm_p1e12=g_norm(1e-12, "norm_p1e12", True), norm_m1e12=g_norm(-1e-12, "norm_m1e12", True),
            norm_p1e3=g_norm(1e-3, "norm_p1e3", False), norm_m1e3=g_norm(-1e-3, "norm_m1e3", False),
            edge_both=g_edge(200, 60, "edge_both"), edge_only=g_edge(0, 80, "edge_only"),
-           edge_none=g_edge(200, 0, "edge_none"))
+           edge_none=g_edge(200, 0, "edge_none"), edge_big_last=g_edge_big_last,
+           edge_pair_first=g_edge_pair(False), edge_pair_empty_last=g_edge_pair(True))
 WANT = dict(six_noisy=_has(ref.GRAD_TOL), far_a=_has(ref.REJECTED), far_b=_has(ref.REJECTED),
             far_c=_has(ref.REJECTED), zero_residual=_has(ref.INVALID), none_valid=_has(ref.INVALID))
 # the first seed (from the base's own start) that admit() and WANT accept: `search` prints them.
@@ -287,7 +333,8 @@ WANT = dict(six_noisy=_has(ref.GRAD_TOL), far_a=_has(ref.REJECTED), far_b=_has(r
 SEEDS = dict(clean=100, outliers=201, knee=301, at_solution=400, six_noisy=506, far_a=605, far_b=705, far_c=801,
              zero_residual=900, none_valid=1000, quat_small=1100, quat_large=1201, par_z=1300, two_family=1400,
              par_oblique=1500, po_line=1601, far5km=1700, tiny=1800, norm_p1e12=1900, norm_m1e12=2001,
-             norm_p1e3=2100, norm_m1e3=2201, edge_both=2306, edge_only=2477, edge_none=2500)
+             norm_p1e3=2100, norm_m1e3=2201, edge_both=2306, edge_only=2477, edge_none=2500,
+             edge_big_last=2603, edge_pair_first=2710, edge_pair_empty_last=2802)
 
 
 COUNTS = (1, 2, 63, 64, 65, 255, 256, 257, 511, 512, 513, 2047, 2048, 2049, 4095, 4096, 4097)

@@ -97,6 +97,8 @@ def associate(last, curr, q, t, valid=None):
     L = np.asarray(last, np.float32)[:, :3].astype(np.float64)
     s = transform_to_last(np.asarray(curr)[:, :3], q, t).astype(np.float64)
     c, m = len(s), len(L)
+    if m == 0:                                   # an empty last frame: no neighbour, nothing kept
+        return np.full(c, -1, np.int64), np.ones(c), np.zeros(c, bool)
     nn = np.zeros(c, np.int64)
     gap = np.ones(c)
     k = min(3, m)

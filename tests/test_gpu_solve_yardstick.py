@@ -143,7 +143,9 @@ def _run(dev, cases, table_mode, capsys, bound=None, what=""):
 def test_solve_families_against_yardstick(dev, family, capsys):
     """every status 0 .. 6, both quaternion-update paths in LM and GN, rank-deficient geometry,
     a scene 5 km out and one below 1 mm, warm starts off the unit sphere, point-to-line blocks
-    (k_solve<true>): brute-force association, one launch per solver and max_iter"""
+    (k_solve<true>; among them a last edge cloud above k_edge_associate's LDS cap, read from
+    global memory, and a two-pair launch whose last pair has an empty last edge cloud):
+    brute-force association, one launch per solver and max_iter"""
     cases = [c for c in rc.solve_cases() if c.family == family]
     seen = set()
     for c in cases:

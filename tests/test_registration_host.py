@@ -35,7 +35,8 @@ def _oracle_solve(O, case, y):
     else:
         last_e, line, lvalid, curr_e = case.edges
         enn = O.correspond(last_e, curr_e, q0, t0)
-        ek = lvalid[enn] != 0
+        ek = enn >= 0                                       # an empty last edge cloud: no neighbour
+        ek[ek] = lvalid[enn[ek]] != 0
         q, t, log = O.solve2(po, pa, n, curr_e[ek, :3], line[enn[ek], :3], line[enn[ek], 3:], mode=MODE[case.solver],
                              max_iter=case.max_iter, q_init=q0, t_init=t0)
         assert int(ek.sum()) == len(y["edges"][0]), case.name
