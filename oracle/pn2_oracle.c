@@ -28,7 +28,7 @@ static float sq3(float dx, float dy, float dz) { return (dx * dx + dy * dy) + dz
 void orc_pn2_fps(const float* xyz, int64_t n, int32_t npoint, int32_t start, float* temp,
                  int32_t* out) {
     for (int64_t i = 0; i < n; ++i) temp[i] = 1e10f;                 /* :80 */
-    int32_t far = start;
+    int32_t far = start < 0 ? 0 : start >= n ? (int32_t)(n - 1) : start;   /* project rule: clamped */
     for (int32_t it = 0; it < npoint; ++it) {
         out[it] = far;                                               /* :84 */
         const float cx = xyz[3 * far], cy = xyz[3 * far + 1], cz = xyz[3 * far + 2];
@@ -67,11 +67,14 @@ void orc_pn2_knn(const float* query, int64_t s, const float* ref, int64_t n, int
     }
 }
 
+/* project rule: an index outside [0, n) reads as 0 (the kernels raise their `bad` flag as well) */
+static float at(const float* row, int64_t n, int32_t i) { return i >= 0 && i < n ? row[i] : 0.0f; }
+
 /* index_points on [C, N]: out[c, j] = feat[c, idx[j]] for g indices. */
 void orc_pn2_gather(const float* feat, int32_t c, int64_t n, const int32_t* idx, int64_t g,
                     float* out) {
     for (int32_t ch = 0; ch < c; ++ch)
-        for (int64_t j = 0; j < g; ++j) out[ch * g + j] = feat[ch * n + idx[j]];
+        for (int64_t j = 0; j < g; ++j) out[ch * g + j] = at(feat + ch * n, n, idx[j]);
 }
 
 /* utils.py:662-663: out[c, j] = (w0 f[i0] + w1 f[i1]) + w2 f[i2]. */
@@ -80,8 +83,8 @@ void orc_pn2_interp3(const float* feat, int32_t c, int64_t m, const int32_t* idx
     for (int32_t ch = 0; ch < c; ++ch)
         for (int64_t j = 0; j < n; ++j) {
             const float* F = feat + ch * m;
-            out[ch * n + j] = (w[3 * j] * F[idx[3 * j]] + w[3 * j + 1] * F[idx[3 * j + 1]]) +
-                              w[3 * j + 2] * F[idx[3 * j + 2]];
+            out[ch * n + j] = (w[3 * j] * at(F, m, idx[3 * j]) + w[3 * j + 1] * at(F, m, idx[3 * j + 1])) +
+                              w[3 * j + 2] * at(F, m, idx[3 * j + 2]);
         }
 }
 

@@ -193,6 +193,8 @@ def upsample_flow(xyz, sparse_xyz, sparse_flow, k=3):
     if not (0 < S <= _abi.PN2_UPSAMPLE_MAX_SPARSE) or not (0 < int(k) <= 16):
         raise ValueError(f"upsample_flow: need 0 < S <= {_abi.PN2_UPSAMPLE_MAX_SPARSE}, 0 < k <= 16")
     out = torch.empty((B, sf.shape[1], N), dtype=torch.float32, device=x.device)
+    if out.numel() == 0:                # no channels (or points): empty tensors have no address
+        return out
     _check(_abi.lib().ssf_pn2_upsample_flow(_stream(x.device), B, N, S, sf.shape[1], int(k),
                                             _ptr(x), _ptr(sx), _ptr(sf), _ptr(out)),
            "upsample_flow")
