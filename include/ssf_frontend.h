@@ -542,6 +542,69 @@ int32_t ssf_icp_batch(ssf_ctx* ctx, void* stream, int32_t n_prob, const float* d
                       const int64_t* d_tgt_off, const int64_t* h_tgt_off,
                       const ssf_icp_params* params, const float* h_guess, double* h_out);
 
+/* Loop detection by appearance (beyond the reference, whose detectLoopFrameID,
+ * src/mapOptmization.cpp:167-197, is a radius search over the estimated key positions and finds
+ * nothing once odometry has drifted past its radius): Scan Context descriptors (Kim & Kim, IROS
+ * 2018) compared exhaustively, every candidate at every column shift.  The
+ * definitions are this project's own.
+ *
+ * ssf_scan_context_batch: the descriptor of n_clouds ragged clouds in the sensor frame, one
+ * launch.
+ *   d_pts [total, point_stride] f32 (point_stride 3 or 4: x, y, z first), cloud c is points
+ *                 [off[c], off[c + 1]) of d_off / h_off (int64, n_clouds + 1, device and host copies)
+ *   d_desc        [n_clouds, SSF_SC_RINGS, SSF_SC_SECTORS] f32
+ * A point with a non-finite coordinate is skipped; with r = sqrt(x^2 + y^2), a point with
+ * r >= max_range is skipped; ring = min(floor(r / (max_range / 20)), 19), sector =
+ * min(floor(phi / (2 pi / 60)), 59) with phi = atan2(y, x) mapped to [0, 2 pi);
+ * desc[ring][sector] = max(0, max over its points of the float sum z + lidar_height); an empty bin
+ * and an empty cloud give 0.  r and phi are evaluated in float: a point within float rounding of a
+ * bin edge may fall on either side of it, every other point's bin is exact and the descriptor bit
+ * for bit that of the definition.
+ *
+ * ssf_scan_context_match: n_query query descriptors against n_db database descriptors.  A column
+ * is valid when one of its bins is above 0 (descriptors are finite and non-negative).  With every
+ * valid column scaled to unit length and J(s) the columns j where query column j and candidate
+ * column (j + s) % 60 are both valid,
+ *   d(s) = 1 - (sum over J(s) of q[:, j] . c[:, (j + s) % 60]) / |J(s)|,   1 when J(s) is empty
+ *   dist = min over s of d(s), shift = the smallest s that attains it
+ * so the query sensor's yaw relative to the candidate's is shift * 2 pi / 60.  Per query the best
+ * candidate is the smallest of 0 .. n_eligible - 1 in the order (dist, index).
+ *   d_query [n_query, 20, 60], d_db [n_db, 20, 60] f32 (d_db may be NULL when n_db == 0)
+ *   d_n_eligible / h_n_eligible  int32 per query, device and host copies, 0 .. n_db
+ *   d_dist, d_shift  nullable together: [n_query, n_db] f32 / int32, every pair; NULL = selection
+ *                 only (then only candidates below the largest n_eligible are compared)
+ *   d_best        per query: index (-1 when n_eligible is 0, then dist 1 and shift 0), dist, shift
+ * Sums have a fixed order and nothing is accumulated atomically: a pair's dist and shift are the
+ * same bits on every run and whatever else is in the call.
+ *
+ * Both are asynchronous on stream.  SSF_E_ARG before any HIP call: a null context or pointer
+ * (d_pts may be NULL for a batch that holds no point), a negative count, point_stride outside
+ * 3..4, offsets that are negative or decrease, max_range or lidar_height not finite, max_range
+ * <= 0, only one of d_dist / d_shift, n_eligible outside 0 .. n_db, n_query * ceil(n_db / 16)
+ * >= 2^31.  n_clouds == 0 and n_query == 0 return SSF_OK without a launch. */
+#define SSF_SC_RINGS 20
+#define SSF_SC_SECTORS 60
+typedef struct {
+    float max_range;        /* 80 m                                                          */
+    float lidar_height;     /* 2 m: added to z so that heights above the ground are positive */
+    float threshold;        /* 0.13: a candidate is accepted when dist < threshold; read by
+                               the caller (ssf.loop.LoopCloser), not by these entry points   */
+} ssf_sc_params;
+typedef struct {
+    int32_t index;
+    float dist;
+    int32_t shift;
+    int32_t reserved;
+} ssf_sc_best;
+int32_t ssf_sc_params_default(ssf_sc_params* out);
+int32_t ssf_scan_context_batch(ssf_ctx* ctx, void* stream, int32_t n_clouds, const float* d_pts,
+                               int32_t point_stride, const int64_t* d_off, const int64_t* h_off,
+                               const ssf_sc_params* params, float* d_desc);
+int32_t ssf_scan_context_match(ssf_ctx* ctx, void* stream, int32_t n_query, const float* d_query,
+                               int32_t n_db, const float* d_db, const int32_t* d_n_eligible,
+                               const int32_t* h_n_eligible, float* d_dist, int32_t* d_shift,
+                               ssf_sc_best* d_best);
+
 /* ssf_pose_graph_batch replaces the pose graph of mapOptmization: the prior and odometry
  * factors of addOdomFactor (src/mapOptmization.cpp:147-165), the loop factor (:274) and
  * runOptimize (:280-293), as batched Gauss-Newton on SE(3) over n_graphs independent graphs,

@@ -15,7 +15,8 @@ LIB = os.path.join(OUT_DIR, "libssf_frontend.so")
 SYNTH_LIB = os.path.join(OUT_DIR, "libssf_synth.so")
 SOURCES = ["abi.hip", "features.hip", "ring_table.hip", "feat_bin.hip", "feat_chunk.hip", "feat_wave.hip",
            "feat_select.hip", "plane_table.hip", "associate.hip", "edges.hip", "solve.hip", "mask_pose.hip",
-           "mask_pose_f64.hip", "kabsch_f32.hip", "subsample.hip", "loop.hip", "pose_graph.hip", "pointnet2.hip", "cost_volume.hip"]
+           "mask_pose_f64.hip", "kabsch_f32.hip", "subsample.hip", "loop.hip", "pose_graph.hip", "pointnet2.hip", "cost_volume.hip",
+           "scan_context.hip"]
 # sources that include another source file
 SRC_DEPS = {"mask_pose_f64.hip": ["mask_pose.hip"]}
 HEADERS = ["ssf_device.hpp", "ssf_internal.hpp", "feat_common.hpp", "reg_knn.hpp", "reg_strips.hpp", "svd3.hpp", "mlp_tile.hpp",

@@ -88,6 +88,8 @@ struct ssf_ctx {
     // working poses, factor records, block factors and right-hand sides of every graph
     DevBuf pgo_desc, pgo_scratch;
     std::vector<ssf::PgoGraph> pgo_h;
+    // scan context (scan_context.hip): the dist / shift rows of a selection-only match
+    DevBuf sc_rows;
     // host RandomState (MT19937, numpy legacy seeding)
     uint32_t mt[624];
     int mt_pos = 625;
@@ -238,7 +240,7 @@ void ssf_destroy(ssf_ctx* c) {
     DevBuf* bufs[] = {&c->rid, &c->hist, &c->ring_off, &c->ring_xyzi, &c->sel, &c->sel_cnt, &c->fix,
                       &c->plane1, &c->off1, &c->cnt1, &c->corr, &c->cidx, &c->pair, &c->start1, &c->vg,
                       &c->icp_cur, &c->icp_key, &c->icp_st, &c->icp_guess, &c->pgo_desc,
-                      &c->pgo_scratch, &c->esel,
+                      &c->pgo_scratch, &c->sc_rows, &c->esel,
                       &c->ecorr, &c->fcnt, &c->fidx, &c->fbits, &c->fcurv, &c->rtab, &c->firr, &c->flmap};
     for (auto& ds : c->dslot) {
         if (ds.used) { (void)hipEventSynchronize(ds.used); (void)hipEventDestroy(ds.used); }
@@ -997,6 +999,74 @@ int32_t ssf_transform_clouds_batch(ssf_ctx* c, void* stream, int32_t n_clouds, c
     hipError_t e = ssf::launch_transform_clouds(s, n_clouds, reinterpret_cast<const float4*>(d_xyzi), d_off,
                                                 h_off[0], total, d_T, reinterpret_cast<float4*>(d_out));
     if (e != hipSuccess) return hip_fail(c, e, "transform_clouds launch");
+    return SSF_OK;
+}
+
+int32_t ssf_sc_params_default(ssf_sc_params* out) {
+    if (!out) return SSF_E_ARG;
+    out->max_range = 80.0f;
+    out->lidar_height = 2.0f;
+    out->threshold = 0.13f;
+    return SSF_OK;
+}
+
+int32_t ssf_scan_context_batch(ssf_ctx* c, void* stream, int32_t n_clouds, const float* d_pts,
+                               int32_t point_stride, const int64_t* d_off, const int64_t* h_off,
+                               const ssf_sc_params* params, float* d_desc) {
+    if (!c) return SSF_E_ARG;
+    if (n_clouds < 0 || point_stride < 3 || point_stride > 4 || !params)
+        return fail(c, SSF_E_ARG, "scan_context_batch: bad arguments (n_clouds >= 0, stride 3 or 4, params)");
+    if (!std::isfinite(params->max_range) || !(params->max_range > 0.0f) || !std::isfinite(params->lidar_height))
+        return fail(c, SSF_E_ARG, "scan_context_batch: max_range must be finite and positive, lidar_height finite");
+    if (n_clouds > 0 && (!d_off || !h_off || !d_desc)) return fail(c, SSF_E_ARG, "scan_context_batch: null pointer");
+    if (n_clouds == 0) return SSF_OK;
+    for (int k = 0; k < n_clouds; ++k)
+        if (h_off[k] < 0 || h_off[k + 1] < h_off[k])
+            return fail(c, SSF_E_ARG, "scan_context_batch: offsets not monotone");
+    if (!d_pts && h_off[n_clouds] != h_off[0])       // a batch of empty clouds has no points
+        return fail(c, SSF_E_ARG, "scan_context_batch: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    ProfScope prof(c, stream);
+    hipError_t e = ssf::launch_sc_describe(s, n_clouds, d_pts, point_stride, d_off, params->max_range,
+                                           params->lidar_height, d_desc);
+    if (e != hipSuccess) return hip_fail(c, e, "scan_context launch");
+    return SSF_OK;
+}
+
+int32_t ssf_scan_context_match(ssf_ctx* c, void* stream, int32_t n_query, const float* d_query,
+                               int32_t n_db, const float* d_db, const int32_t* d_n_eligible,
+                               const int32_t* h_n_eligible, float* d_dist, int32_t* d_shift,
+                               ssf_sc_best* d_best) {
+    if (!c) return SSF_E_ARG;
+    if (n_query < 0 || n_db < 0) return fail(c, SSF_E_ARG, "scan_context_match: negative count");
+    if ((d_dist == nullptr) != (d_shift == nullptr))
+        return fail(c, SSF_E_ARG, "scan_context_match: d_dist and d_shift are given or null together");
+    if (n_query > 0 && (!d_query || !d_n_eligible || !h_n_eligible || !d_best || (n_db > 0 && !d_db)))
+        return fail(c, SSF_E_ARG, "scan_context_match: null pointer");
+    if (n_query == 0) return SSF_OK;
+    int32_t max_el = 0;
+    for (int k = 0; k < n_query; ++k) {
+        if (h_n_eligible[k] < 0 || h_n_eligible[k] > n_db)
+            return fail(c, SSF_E_ARG, "scan_context_match: n_eligible outside 0 .. n_db");
+        max_el = std::max(max_el, h_n_eligible[k]);
+    }
+    const int n_cols = d_dist ? n_db : max_el;
+    if ((int64_t)n_query * ((n_cols + 15) / 16) >= ((int64_t)1 << 31))
+        return fail(c, SSF_E_ARG, "scan_context_match: too many pairs for one call");
+    hipStream_t s = (hipStream_t)stream;
+    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    float* dist = d_dist;
+    int32_t* shift = d_shift;
+    if (!dist && n_cols > 0) {
+        const size_t rows = (size_t)n_query * (size_t)n_db;
+        SSF_TRY_HIP(c, c->sc_rows.ensure(rows * (sizeof(float) + sizeof(int32_t))), "alloc scan context rows");
+        dist = c->sc_rows.as<float>();
+        shift = reinterpret_cast<int32_t*>(dist + rows);
+    }
+    ProfScope prof(c, stream);
+    hipError_t e = ssf::launch_sc_match(s, n_query, d_query, n_db, n_cols, d_db, d_n_eligible, dist, shift, d_best);
+    if (e != hipSuccess) return hip_fail(c, e, "scan_context_match launch");
     return SSF_OK;
 }
 

@@ -273,6 +273,14 @@ hipError_t launch_subsample(hipStream_t s, int n_frames, const float* pts, int s
                             const int64_t* frame_off, const uint8_t* cls, int nb, float z_min,
                             int use_z, int quota, uint64_t seed, const uint64_t* h_tag, int key_bits,
                             int32_t* idx, float* xyz, int32_t* n_out, int32_t* status);
+// ---- launchers (scan_context.hip): the Scan Context descriptor of n_clouds ragged clouds, one
+// work-group per cloud; and the exhaustive comparison of n_query descriptors with candidates
+// 0 .. n_cols - 1 of n_db (dist / shift rows of n_db entries, never null here) followed by the
+// selection over each query's eligible prefix.  n_cols == 0 launches the selection only.
+hipError_t launch_sc_describe(hipStream_t s, int n_clouds, const float* pts, int stride, const int64_t* off,
+                              float max_range, float lidar_height, float* desc);
+hipError_t launch_sc_match(hipStream_t s, int n_query, const float* query, int n_db, int n_cols, const float* db,
+                           const int32_t* n_eligible, float* dist, int32_t* shift, ssf_sc_best* best);
 size_t mask_sync_bytes(int n_frames);
 size_t mask_parts_bytes(int n_frames, int G);
 // The Lloyd record / queue buffer of a launch of `total` points in n_frames frames: 8-byte

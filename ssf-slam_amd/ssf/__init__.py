@@ -13,7 +13,10 @@ from . import pointnet2  # noqa: F401  (TFlow point-set operators: pointutils su
 from . import tflow  # noqa: F401  (the TFlow network: cost volume, warping, flow regressor)
 from .tflow import CostVolume, PointWarping, RefineFlowRegressor, TFlow  # noqa: F401
 from . import asf  # noqa: F401  (the ActiveSceneFlow chain: subsample, TFlow, mask, pose)
+from . import scan_context  # noqa: F401  (loop detection by appearance: Scan Context descriptors)
+from .scan_context import ScanContextDB  # noqa: F401
 
 __all__ = ["Frontend", "PlaneBatch", "frame_offsets", "identity_poses", "register_plan", "SSFError",
            "mask_and_pose", "slove_RT_by_SVD", "loop", "MapCloud", "pointnet2"]
 __all__ += ["tflow", "CostVolume", "PointWarping", "RefineFlowRegressor", "TFlow", "asf"]
+__all__ += ["scan_context", "ScanContextDB"]

@@ -43,7 +43,12 @@ EXPORTS = [
     "ssf_transform_clouds_batch", "ssf_subsample_batch",
     "ssf_pgo_robust_default", "ssf_pose_graph_batch_robust",
     "ssf_pgo_lm_default", "ssf_pose_graph_batch_lm",
+    "ssf_sc_params_default", "ssf_scan_context_batch", "ssf_scan_context_match",
 ]
+# ssf_scan_context_*: descriptor shape; ssf_sc_best as four 32-bit words per query
+SC_RINGS, SC_SECTORS = 20, 60
+SC_BEST_STRIDE = 4
+SC_BEST = dict(INDEX=0, DIST=1, SHIFT=2)
 # ssf_subsample_batch: limits and per-frame status codes
 SAMPLE_MAX_NB, SAMPLE_MAX_POINTS = 8192, 1 << 24
 SAMPLE_OK, SAMPLE_EMPTY, SAMPLE_SHORT = 0, -1, -2
@@ -92,6 +97,10 @@ class PgoRobust(C.Structure):
 class PgoLm(C.Structure):
     _fields_ = [("radius0", C.c_double), ("min_relative_decrease", C.c_double), ("max_radius", C.c_double),
                 ("min_radius", C.c_double)]
+
+
+class ScParams(C.Structure):
+    _fields_ = [("max_range", C.c_float), ("lidar_height", C.c_float), ("threshold", C.c_float)]
 
 
 class IcpParams(C.Structure):
@@ -235,6 +244,12 @@ def lib():
                                                                       C.POINTER(PgoRobust), vp,
                                                                       C.POINTER(PgoLm), vp]
     L.ssf_pose_graph_batch_lm.restype = i32
+    L.ssf_sc_params_default.argtypes = [C.POINTER(ScParams)]
+    L.ssf_sc_params_default.restype = i32
+    L.ssf_scan_context_batch.argtypes = [vp, vp, i32, vp, i32, vp, vp, C.POINTER(ScParams), vp]
+    L.ssf_scan_context_batch.restype = i32
+    L.ssf_scan_context_match.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.ssf_scan_context_match.restype = i32
     L.ssf_pn2_last_error.argtypes = []
     L.ssf_pn2_last_error.restype = C.c_char_p
     L.ssf_pn2_furthest_point_sample.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]

@@ -201,8 +201,17 @@ def node_main(exe: str, argv=None):
         map_cloud = bool(rospy.get_param("~MAP_CLOUD")) if rospy.has_param("~MAP_CLOUD") else False
         topics = ["/map_odom_res3", "/map_frame_res3", "/map_laser_path_res3"]
         pub = rosbridge.RosPublisher(topics + (["/sum_map_cloud_res3"] if map_cloud else []))
-        node = nodes.MapOptimizationNode(pub, device=a.device, tum_path=path,
-                                         **(dict(map_cloud=True) if map_cloud else {}))
+        # ~MAP_DETECTOR (not a reference param, default radius): "scan-context[:THRESHOLD]" finds
+        # loops by Scan Context descriptors of /velodyne_points instead of the radius search
+        mkw = dict(map_cloud=True) if map_cloud else {}
+        if rospy.has_param("~MAP_DETECTOR"):
+            from .scan_context import parse_detector
+            det, thr = parse_detector(rospy.get_param("~MAP_DETECTOR"))
+            if det != "radius":
+                mkw.update(map_detector=det, map_sc_threshold=thr)
+        node = nodes.MapOptimizationNode(pub, device=a.device, tum_path=path, **mkw)
+        if "map_detector" in mkw:
+            rospy.Subscriber("/velodyne_points", sensor_msgs.PointCloud2, node.on_scan, queue_size=10)
         rospy.Subscriber("/plane_frame_cloud2", sensor_msgs.PointCloud2, node.on_plane_cloud,
                          queue_size=10)                               # mapOptmization.cpp:473
         rospy.Subscriber("/frame_odom2", nav_msgs.Odometry,

@@ -17,6 +17,9 @@ control under them (``pgo=pgo_params(...)`` their iteration limit).  ``LoopClose
 accumulated map cloud (mapCloudPtr: updateKeyPose :309-311, the rebuild of
 correctPoses :320-325) on the device in an ``ssf.MapCloud``; a new keyframe
 goes into the map at its stored key pose (the reference places it at its iSAM2 estimate).
+``LoopCloser(detector="scan_context")`` replaces the radius search of detectLoopFrameID, which
+finds nothing once the odometry has drifted past its 15 m, by place recognition on Scan Context
+descriptors of the raw scans (``ssf.scan_context``); the default stays the radius.
 
 Pose helpers restate pcl/common/eigen.h: getTransformation (roll/pitch/yaw -> affine,
 yaw * pitch * roll) and getTranslationAndEulerAngles.  Key poses are stored in float, as the
@@ -322,6 +325,8 @@ class LoopConstraint:
     between: np.ndarray          # poseFrom.between(poseTo), 4x4
     noise: float                 # ICP fitness score (diagonal variances, :257-259)
     correction: np.ndarray       # correctionLidarFrame, 4x4
+    shift: int | None = None     # detector="scan_context": the column shift of the match (yaw = shift * 6 deg)
+    dist: float | None = None    # and its Scan Context distance
 
 
 @dataclass
@@ -358,8 +363,28 @@ class LoopCloser:
     # pose: appended per keyframe, rebuilt in one launch when the poses are rewritten
     map_cloud: bool = False
     map: object | None = None                          # ssf.MapCloud when map_cloud, else None
+    # detector="radius": detectLoopFrameID's radius search over the estimated key positions (the
+    # reference; it finds nothing once odometry has drifted past `radius`).  "scan_context": place
+    # recognition by appearance (ssf.scan_context): every keyframe's descriptor is
+    # computed from the frame's raw scan (process(scan=...)) and kept on the device, a new keyframe is
+    # compared with every keyframe of the eligible prefix, and a candidate is accepted when its
+    # distance is below sc.threshold (sc: ssf.scan_context.sc_params; None: the defaults)
+    detector: str = "radius"
+    sc: object | None = None
+    sc_db: object | None = None                        # ssf.scan_context.ScanContextDB
+    sc_match: tuple | None = None                      # (key_pre, dist, shift) of the last accepted match
 
     def __post_init__(self):
+        if self.detector not in ("radius", "scan_context"):
+            raise ValueError(f"LoopCloser: detector is radius or scan_context, not {self.detector!r}")
+        if self.detector == "scan_context":
+            from .scan_context import ScanContextDB, sc_params
+            if self.sc is None:
+                self.sc = sc_params()
+            if self.sc_db is None:
+                self.sc_db = ScanContextDB(self.fe)
+        elif self.sc is not None:
+            raise ValueError("LoopCloser: sc belongs to detector=\"scan_context\"")
         if self.map_cloud and self.map is None:
             from .map_cloud import MapCloud
             self.map = MapCloud(self.fe)
@@ -389,10 +414,13 @@ class LoopCloser:
         return not (abs(r) < 0.01 and abs(p) < 0.01 and abs(yw) < 0.01 and math.sqrt(x * x + y * y + z * z) < 1)
 
     def detect_loop(self):
-        """detectLoopFrameID (:167-197): radius search over key positions (nearest first)."""
+        """detectLoopFrameID (:167-197): radius search over key positions (nearest first).
+        detector="scan_context": the nearest descriptor of the eligible prefix instead."""
         cur = len(self.key6d) - 1
         if cur in self.loop_index:
             return None
+        if self.detector == "scan_context":
+            return self._detect_loop_scan_context(cur)
         pos = np.array([k[:3] for k in self.key6d], np.float32)
         d2 = ((pos - pos[cur]) ** 2).sum(1)
         cand = np.nonzero(d2 < np.float32(self.radius * self.radius))[0]   # FLANN: dist < r^2
@@ -404,6 +432,21 @@ class LoopCloser:
                 break
         if pre == -1 or pre == cur:
             return None
+        self.loop_record_index = cur + 2
+        return cur, pre
+
+    def _detect_loop_scan_context(self, cur):
+        """The new keyframe's descriptor against the leading keyframes whose stamp is more than
+        time_gap older than its own (the prefix stops at the first keyframe that is not); the
+        smallest (dist, index) is accepted when dist < sc.threshold."""
+        from .scan_context import eligible_prefix
+        n_el = eligible_prefix([k[6] for k in self.key6d[:cur]], self.key6d[cur][6], self.time_gap)
+        if n_el == 0:
+            return None
+        pre, dist, shift = self.sc_db.query(self.sc_db.descriptors()[cur], n_el)
+        if pre < 0 or not dist < self.sc.threshold:
+            return None
+        self.sc_match = (pre, dist, shift)
         self.loop_record_index = cur + 2
         return cur, pre
 
@@ -429,7 +472,14 @@ class LoopCloser:
         pre_cloud = self.local_map(pre, self.search_num)
         if cur_cloud.shape[0] < 300 or pre_cloud.shape[0] < 1000:
             return None
-        r = icp(self.fe, cur_cloud, pre_cloud)
+        if self.detector == "scan_context":
+            # the keyframes may lie far apart in the drifted map frame: start ICP with the current
+            # cloud placed at the candidate's pose under the yaw the match recovered
+            yaw = self.sc_match[2] * (2.0 * math.pi / 60.0)
+            guess = self._T6(pre) @ get_transformation(0.0, 0.0, 0.0, 0.0, 0.0, yaw) @ np.linalg.inv(self._T6(cur))
+            r = icp(self.fe, cur_cloud, pre_cloud, guess=guess)
+        else:
+            r = icp(self.fe, cur_cloud, pre_cloud)
         if not r["converged"] or r["fitness"] > 0.2:
             return None
         corr = r["T"].astype(np.float64)
@@ -437,6 +487,8 @@ class LoopCloser:
         t_correct = corr @ self._T6(cur)
         pose_from = get_transformation(*get_translation_and_euler_angles(t_correct))
         c = LoopConstraint(cur, pre, between(pose_from, self._T6(pre)), float(np.float32(r["fitness"])), corr)
+        if self.detector == "scan_context":
+            c.dist, c.shift = self.sc_match[1], self.sc_match[2]
         self.loop_index[cur] = pre
         self.constraints.append(c)
         return c
@@ -476,9 +528,15 @@ class LoopCloser:
             self.rebuild_map()
         return self._T6(-1)
 
-    def process(self, plane_xyzi: torch.Tensor, q_xyzw, t, stamp: float):
+    def process(self, plane_xyzi: torch.Tensor, q_xyzw, t, stamp: float, scan: torch.Tensor | None = None):
         """One synchronised (/plane_frame_cloud2, /frame_odom2) pair (cloudThread :429-451 +
-        mapOptimization :455-467).  Returns (T_map_0_curr, constraint or None, is_key)."""
+        mapOptimization :455-467).  Returns (T_map_0_curr, constraint or None, is_key).
+        scan: the frame's raw points in the sensor frame, device [n, 3] or [n, 4] float32; needed by
+        detector="scan_context" (ValueError without it) and not read otherwise.  The descriptor
+        is never built from plane_xyzi: with a few hundred planar points most columns hold one
+        occupied ring, two such columns have cosine 1, and every candidate comes out at distance 0."""
+        if self.detector == "scan_context" and scan is None:
+            raise ValueError("LoopCloser(detector=\"scan_context\"): process needs scan=, the frame's raw points")
         T = self.trans_loop_adjust @ pose_from_quat(q_xyzw, t)
         if not self.is_key_frame(T):
             return T, None, False
@@ -490,6 +548,9 @@ class LoopCloser:
             self.key_frames.append(plane_xyzi.contiguous())
         if self.optimize:
             self._add_odom_factor((x, y, z, r, p, yw))
+        if self.detector == "scan_context":
+            from .scan_context import describe_one
+            self.sc_db.append(describe_one(self.fe, scan, self.sc))
         c = self.add_loop_factor()
         rebuilt = False
         if c is not None:                                   # correctPoses (:321-326)

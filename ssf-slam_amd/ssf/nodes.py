@@ -268,11 +268,17 @@ class MapOptimizationNode:
     (with optimize): their max_iter (default 8), the attempts under step control.
     map_cloud=True: the accumulated map (mapCloudPtr) is kept on the device (``closer.map``)
     and its 0.4 m VoxelGrid is published on /sum_map_cloud_res3 for every keyframe whose pair
-    count numFrame (first pair = 1) is a multiple of 5 (publishResult :387-397)."""
+    count numFrame (first pair = 1) is a multiple of 5 (publishResult :387-397).
+    map_detector="scan_context" (default "radius", the reference's search over key positions):
+    loops are found by Scan Context descriptors of the raw scans (ssf.scan_context, DESIGN.md
+    §6.12); the node then also takes /velodyne_points (on_scan), pairs each scan with its plane
+    cloud by stamp and hands it to the closer; map_sc_threshold: the acceptance distance
+    (default: ssf_sc_params')."""
 
     def __init__(self, publish, device=None, frontend: Frontend | None = None,
                  tum_path: str | None = None, optimize: bool = False, map_cloud: bool = False,
-                 map_robust=None, map_lm=None, map_iters: int | None = None):
+                 map_robust=None, map_lm=None, map_iters: int | None = None,
+                 map_detector: str = "radius", map_sc_threshold: float | None = None):
         from .loop import LoopCloser, get_translation_and_euler_angles, pgo_params  # noqa: F401
         self.publish = publish
         self.fe = frontend or Frontend(64, device=device)
@@ -293,7 +299,15 @@ class MapOptimizationNode:
             kw["map_cloud"] = True
         if map_robust is not None:
             kw["robust"] = map_robust
+        if map_detector not in ("radius", "scan_context"):
+            raise ValueError(f"map_detector is radius or scan_context, not {map_detector!r}")
+        if map_sc_threshold is not None and map_detector != "scan_context":
+            raise ValueError("map_sc_threshold is the acceptance distance of map_detector=\"scan_context\"")
+        if map_detector == "scan_context":
+            from .scan_context import sc_params
+            kw.update(detector="scan_context", sc=sc_params(threshold=map_sc_threshold))
         self.closer = LoopCloser(self.fe, **kw)
+        self.scans = []                           # recent /velodyne_points (map_detector="scan_context")
         self.map_cloud = bool(map_cloud)
         self.num_frame = 0                        # numFrame (:433): synchronised pairs
         self.map_published = 0
@@ -309,6 +323,27 @@ class MapOptimizationNode:
         self.odoms.append(msg)
         self._drain()
 
+    def on_scan(self, msg):
+        """/velodyne_points: the raw scan the Scan Context descriptor is built from; not kept
+        under the radius detector."""
+        if self.closer.detector != "scan_context":
+            return
+        self.scans.append(msg)
+        del self.scans[:-16]
+        self._drain()
+
+    def _scan_for(self, tp):
+        """The kept scan stamped within 5 ms of tp -> (found, msg).  Without one: not found while
+        no later scan has come either (it may still arrive); else the nearest in stamp (its own
+        was lost)."""
+        if not self.scans:
+            return False, None
+        dt = [(s[0] - tp[0]) + (s[1] - tp[1]) * 1e-9 for s in (sio.stamp_of(m.header) for m in self.scans)]
+        k = min(range(len(dt)), key=lambda i: abs(dt[i]))
+        if abs(dt[k]) > 0.005 and max(dt) < 0.0:
+            return False, None
+        return True, self.scans[k]
+
     def _drain(self):
         import numpy as np
         from .loop import transform_cloud
@@ -318,12 +353,18 @@ class MapOptimizationNode:
             tp, to = sio.stamp_of(pm.header), sio.stamp_of(om.header)
             if abs((tp[0] - to[0]) + (tp[1] - to[1]) * 1e-9) > 0.005:    # time sync (:436-439)
                 return
+            kw = {}
+            if self.closer.detector == "scan_context":
+                found, sm = self._scan_for(tp)
+                if not found:                      # the pair's scan has not come yet: on_scan drains again
+                    return
+                kw["scan"] = torch.from_numpy(np.array(sio.cloud_xyz(sm))).to(self.fe.device)  # msg bytes are read-only
             self.planes.pop(0)
             self.odoms.pop(0)
             xyzi = torch.from_numpy(sio.cloud_xyzi(pm)).to(self.fe.device)
             stamp = tp[0] + tp[1] * 1e-9
             self.num_frame += 1
-            T, _, is_key = self.closer.process(xyzi, om.pose.orientation, om.pose.position, stamp)
+            T, _, is_key = self.closer.process(xyzi, om.pose.orientation, om.pose.position, stamp, **kw)
             q = Rotation.from_matrix(T[:3, :3]).as_quat()                  # x, y, z, w
             hdr = sio.Header(tp[0], tp[1], "map")
             pose = Pose(tuple(float(v) for v in T[:3, 3]), tuple(float(v) for v in q))
@@ -380,7 +421,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
                  rate_hz: float = 10.0, launch: str = "onlyPC", map_tum_path: str | None = None,
                  truncate_results: bool = False, map_optimize: bool = False, map_cloud: bool = False,
                  weights=None, n_points: int = 8192, map_robust=None, map_lm=None,
-                 map_iters: int | None = None):
+                 map_iters: int | None = None, map_detector: str = "radius",
+                 map_sc_threshold: float | None = None):
     """Replay a DATASET_PATH directory through the node graph of launch/run_<launch>.launch:
       onlyPC: PointCloudOdometry_onlyPC -> frameFeature -> lidarOdometry_onlyPC (registration)
       noSeg:  PointCloudOdometry_noSeg (GMM mask + Kabsch -> /frame_odom1) -> frameFeature ->
@@ -394,7 +436,9 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
     plus mapOptmization when `map_tum_path` is given (map_optimize: with the GPU pose-graph
     optimisation of its loop closures; map_robust: an ssf.loop.pgo_robust loss on their loop
     edges, map_lm: an ssf.loop.pgo_lm step control for those solves, map_iters: their max_iter;
-    all three need map_optimize).  Stamps are synthetic and monotone (frame k
+    all three need map_optimize; map_detector="scan_context": its loops are found by Scan Context
+    descriptors of the /velodyne_points scans instead of the radius search, map_sc_threshold the
+    acceptance distance).  Stamps are synthetic and monotone (frame k
     at k / rate_hz; the reference uses wall-clock ros::Time::now()).  The /frame_odom2 poses are
     appended to `tum_path` as TUM lines (like the reference, an existing file is extended unless
     truncate_results=True).
@@ -415,6 +459,12 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
         raise ValueError("map_iters is the iteration limit of the pose-graph solve: it needs map_optimize")
     if map_iters is not None and int(map_iters) <= 0:
         raise ValueError("map_iters must be positive")
+    if map_detector not in ("radius", "scan_context"):
+        raise ValueError(f"map_detector is radius or scan_context, not {map_detector!r}")
+    if map_detector != "radius" and map_tum_path is None:
+        raise ValueError("map_detector chooses mapOptmization's loop detector: pass map_tum_path")
+    if map_sc_threshold is not None and map_detector != "scan_context":
+        raise ValueError("map_sc_threshold is the acceptance distance of map_detector=\"scan_context\"")
     src_mode, odo_kind, keys = LAUNCH_GRAPHS[launch][:3]
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     bus = Bus()
@@ -464,9 +514,13 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
             mkw["map_lm"] = map_lm
         if map_iters is not None:
             mkw["map_iters"] = map_iters
+        if map_detector != "radius":
+            mkw.update(map_detector=map_detector, map_sc_threshold=map_sc_threshold)
         mo = MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None, **mkw)
         bus.subscribe("/plane_frame_cloud2", mo.on_plane_cloud)
         bus.subscribe("/frame_odom2", mo.on_odom)
+        if map_detector == "scan_context":           # after frameFeature: the pair waits for its scan
+            bus.subscribe("/velodyne_points", mo.on_scan)
     period_ns = int(round(1e9 / rate_hz))
     metrics = []
     for fr in sio.NpzSequence(root, keys=keys, device=dev):

@@ -2,8 +2,9 @@
 sequence through the device front-end as one of the reference's launch files wires its nodes
 (launch/run_onlyPC.launch, run_noSeg.launch, run_Seg.launch, run_noSeg_ActiveSceneFlow.launch,
 run_Seg_ActiveSceneFlow.launch with --weights; ssf.nodes.LAUNCH_GRAPHS) and append
-/frame_odom2 to a TUM trajectory (optionally with mapOptmization's loop closure, and with
---map-cloud its accumulated map cloud saved as an npy file)."""
+/frame_odom2 to a TUM trajectory (optionally with mapOptmization's loop closure, with
+--map-cloud its accumulated map cloud saved as an npy file, and with --map-detector scan-context
+its loops found by Scan Context descriptors instead of the radius search)."""
 from __future__ import annotations
 
 import argparse
@@ -44,6 +45,11 @@ def main(argv=None):
     ap.add_argument("--map-cloud", default=None, metavar="FILE.npy",
                     help="with --map-tum: keep the accumulated map cloud on the GPU, publish its 0.4 m "
                          "VoxelGrid on /sum_map_cloud_res3 and save the final one as float32 [M, 4]")
+    ap.add_argument("--map-detector", default=None, metavar="radius|scan-context[:THRESHOLD]",
+                    help="with --map-tum: how mapOptmization finds loops; radius (default) is the "
+                         "reference's 15 m search over the estimated key positions, scan-context compares "
+                         "Scan Context descriptors of the raw scans on the GPU and also finds a loop "
+                         "after the odometry has drifted; THRESHOLD the acceptance distance (default 0.13)")
     ap.add_argument("--weights", default=None, metavar="FILE",
                     help="the ActiveSceneFlow launches: TFlow checkpoint (a state dict with the "
                          "reference's keys, a DataParallel `module.` prefix accepted)")
@@ -83,6 +89,18 @@ def main(argv=None):
         if a.map_iters <= 0:
             ap.error("--map-iters: must be positive")
         kw["map_iters"] = a.map_iters
+    detector = None
+    if a.map_detector is not None:
+        if a.map_tum is None:
+            ap.error("--map-detector needs --map-tum")
+        from .scan_context import parse_detector
+        try:
+            detector, thr = parse_detector(a.map_detector)
+        except ValueError as e:
+            ap.error(f"--map-detector: {e}")
+        kw["map_detector"] = detector
+        if thr is not None:
+            kw["map_sc_threshold"] = thr
     torch.cuda.set_device(a.device)
     from .nodes import ASF_LAUNCHES
     if a.launch in ASF_LAUNCHES:
@@ -110,7 +128,14 @@ def main(argv=None):
             np.save(f, res["map_cloud"])
         extra["map_cloud"] = {"file": a.map_cloud, "points": int(res["map_cloud"].shape[0]),
                               "keyframes": int(res["map_cloud_keyframes"])}
-    if res.get("flow_metrics"):                      # the dataset carries gt: the mean of each metric
+    if detector is not None:                         # "loops" below: the loops it closed
+        extra["map_detector"] = {"detector": detector, "loops_closed": len(res["loops"])}
+        if detector == "scan_context":
+            extra["map_detector"].update(
+                threshold=kw.get("map_sc_threshold", 0.13),
+                matches=[{"key_cur": c.key_cur, "key_pre": c.key_pre, "dist": c.dist, "shift": c.shift}
+                         for c in res["loops"]])
+    if res.get("flow_metrics"):                     # the dataset carries gt: the mean of each metric
         fm = res["flow_metrics"]
         extra["flow_metrics"] = {k: sum(m[k] for m in fm) / len(fm) for k in fm[0]}
     print(json.dumps({"launch": a.launch, "tum": a.tum, "tum_mode": "truncate" if a.truncate else "append",
