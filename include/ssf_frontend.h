@@ -581,9 +581,25 @@ int32_t ssf_icp_batch(ssf_ctx* ctx, void* stream, int32_t n_prob, const float* d
  * (d_pts may be NULL for a batch that holds no point), a negative count, point_stride outside
  * 3..4, offsets that are negative or decrease, max_range or lidar_height not finite, max_range
  * <= 0, only one of d_dist / d_shift, n_eligible outside 0 .. n_db, n_query * ceil(n_db / 16)
- * >= 2^31.  n_clouds == 0 and n_query == 0 return SSF_OK without a launch. */
+ * >= 2^31.  n_clouds == 0 and n_query == 0 return SSF_OK without a launch.
+ *
+ * ssf_scan_context_match_topk: the arguments of ssf_scan_context_match plus k and exclusion; per
+ * query the k best candidates that are places of their own.  For a query with eligible prefix
+ * [0, n_eligible), k in 1 .. SSF_SC_MAX_TOPK and exclusion E >= 0: walk the candidates in the
+ * total order (dist, index), a NaN distance counting as +infinity; take a candidate when its
+ * index differs by more than E from every index already taken; stop at k taken or when the prefix
+ * is exhausted.
+ *   d_best        [n_query * k], query-major: slot j of a query is its j-th taken candidate
+ *                 (index, dist, shift), dist and shift copied from the rows; an unfilled slot is
+ *                 (-1, 1.0f, 0), the record ssf_scan_context_match writes without a candidate
+ * Slot 0 is ssf_scan_context_match's d_best bit for bit, for every E; E = 0 gives the plain k
+ * smallest.  d_dist / d_shift as above (NULL together = selection only, the rows then live in
+ * context scratch).  The rows come from the same launch as ssf_scan_context_match's.  SSF_E_ARG
+ * before any HIP call, with nothing written: k < 1, k > SSF_SC_MAX_TOPK, exclusion < 0 and every
+ * argument error of ssf_scan_context_match.  n_query == 0 returns SSF_OK without a launch. */
 #define SSF_SC_RINGS 20
 #define SSF_SC_SECTORS 60
+#define SSF_SC_MAX_TOPK 8
 typedef struct {
     float max_range;        /* 80 m                                                          */
     float lidar_height;     /* 2 m: added to z so that heights above the ground are positive */
@@ -604,6 +620,10 @@ int32_t ssf_scan_context_match(ssf_ctx* ctx, void* stream, int32_t n_query, cons
                                int32_t n_db, const float* d_db, const int32_t* d_n_eligible,
                                const int32_t* h_n_eligible, float* d_dist, int32_t* d_shift,
                                ssf_sc_best* d_best);
+int32_t ssf_scan_context_match_topk(ssf_ctx* ctx, void* stream, int32_t n_query, const float* d_query,
+                                    int32_t n_db, const float* d_db, const int32_t* d_n_eligible,
+                                    const int32_t* h_n_eligible, float* d_dist, int32_t* d_shift,
+                                    ssf_sc_best* d_best, int32_t k, int32_t exclusion);
 
 /* ssf_pose_graph_batch replaces the pose graph of mapOptmization: the prior and odometry
  * factors of addOdomFactor (src/mapOptmization.cpp:147-165), the loop factor (:274) and

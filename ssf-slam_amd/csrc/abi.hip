@@ -1070,6 +1070,46 @@ int32_t ssf_scan_context_match(ssf_ctx* c, void* stream, int32_t n_query, const 
     return SSF_OK;
 }
 
+int32_t ssf_scan_context_match_topk(ssf_ctx* c, void* stream, int32_t n_query, const float* d_query,
+                                    int32_t n_db, const float* d_db, const int32_t* d_n_eligible,
+                                    const int32_t* h_n_eligible, float* d_dist, int32_t* d_shift,
+                                    ssf_sc_best* d_best, int32_t k, int32_t exclusion) {
+    if (!c) return SSF_E_ARG;
+    if (k < 1 || k > SSF_SC_MAX_TOPK)
+        return fail(c, SSF_E_ARG, "scan_context_match_topk: k outside 1 .. SSF_SC_MAX_TOPK");
+    if (exclusion < 0) return fail(c, SSF_E_ARG, "scan_context_match_topk: negative exclusion");
+    if (n_query < 0 || n_db < 0) return fail(c, SSF_E_ARG, "scan_context_match_topk: negative count");
+    if ((d_dist == nullptr) != (d_shift == nullptr))
+        return fail(c, SSF_E_ARG, "scan_context_match_topk: d_dist and d_shift are given or null together");
+    if (n_query > 0 && (!d_query || !d_n_eligible || !h_n_eligible || !d_best || (n_db > 0 && !d_db)))
+        return fail(c, SSF_E_ARG, "scan_context_match_topk: null pointer");
+    if (n_query == 0) return SSF_OK;
+    int32_t max_el = 0;
+    for (int q = 0; q < n_query; ++q) {
+        if (h_n_eligible[q] < 0 || h_n_eligible[q] > n_db)
+            return fail(c, SSF_E_ARG, "scan_context_match_topk: n_eligible outside 0 .. n_db");
+        max_el = std::max(max_el, h_n_eligible[q]);
+    }
+    const int n_cols = d_dist ? n_db : max_el;
+    if ((int64_t)n_query * ((n_cols + 15) / 16) >= ((int64_t)1 << 31))
+        return fail(c, SSF_E_ARG, "scan_context_match_topk: too many pairs for one call");
+    hipStream_t s = (hipStream_t)stream;
+    SSF_TRY_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+    float* dist = d_dist;
+    int32_t* shift = d_shift;
+    if (!dist && n_cols > 0) {
+        const size_t rows = (size_t)n_query * (size_t)n_db;
+        SSF_TRY_HIP(c, c->sc_rows.ensure(rows * (sizeof(float) + sizeof(int32_t))), "alloc scan context rows");
+        dist = c->sc_rows.as<float>();
+        shift = reinterpret_cast<int32_t*>(dist + rows);
+    }
+    ProfScope prof(c, stream);
+    hipError_t e = ssf::launch_sc_match_topk(s, n_query, d_query, n_db, n_cols, d_db, d_n_eligible, dist, shift, k,
+                                             exclusion, d_best);
+    if (e != hipSuccess) return hip_fail(c, e, "scan_context_match_topk launch");
+    return SSF_OK;
+}
+
 int32_t ssf_icp_params_default(ssf_icp_params* out) {
     if (!out) return SSF_E_ARG;
     out->max_iter = 100;            // mapOptmization.cpp:225-228

@@ -15,6 +15,8 @@
 //   k_sc_match     one wave per (query, candidate) pair: normalise the candidate's columns on
 //                  load, G by MFMA, G parked in LDS, lane s sums its diagonal in the order j = 0..59.
 //   k_sc_select    one work-group per query: the smallest (dist, index) of the eligible prefix.
+//   k_sc_select_topk  one work-group per query: the K smallest whose indices lie more than an
+//                  exclusion window apart, taken greedily in the same order.
 //
 // Nothing is exchanged between work-groups, there are no global or float atomics and every sum
 // has a fixed order: a pair's dist and shift are the same bits whatever else is in the batch.
@@ -246,24 +248,115 @@ __global__ __launch_bounds__(kScSelT) void k_sc_select(const float* __restrict__
     }
 }
 
+// Greedy top-K with an exclusion window (include/ssf_frontend.h): k rounds of k_sc_select's
+// reduction over the candidates whose index differs by more than `exclusion` from every index
+// taken so far.  The taken indices sit in LDS (copied to registers at the start of a round); every
+// thread reads the round's winner from the four wave slots, so the round count and the early end
+// are uniform.  The row is read again in every round.  Round 0 has nothing taken and is
+// k_sc_select's reduction, comparison for comparison: slot 0 is its `best`.
+constexpr int kScMaxTopk = SSF_SC_MAX_TOPK;
+
+__global__ __launch_bounds__(kScSelT) void k_sc_select_topk(const float* __restrict__ dist,
+                                                            const int32_t* __restrict__ shift, int n_db,
+                                                            const int32_t* __restrict__ n_eligible, int k,
+                                                            int exclusion, ssf_sc_best* __restrict__ best) {
+    __shared__ float sd[kScSelT / 64];
+    __shared__ int si[kScSelT / 64];
+    __shared__ int taken[kScMaxTopk];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int q = blockIdx.x;
+    int n = n_eligible[q];
+    n = n < 0 ? 0 : (n > n_db ? n_db : n);           // the host checked its copy
+    const float* drow = dist + (int64_t)q * n_db;
+    const int32_t* srow = shift + (int64_t)q * n_db;
+    ssf_sc_best* out = best + (int64_t)q * k;
+    int n_taken = 0;
+    for (; n_taken < k; ++n_taken) {
+        float bd = INFINITY;
+        int bi = INT_MAX;
+        int tk[kScMaxTopk];                              // the taken indices in registers for this round
+#pragma unroll
+        for (int j = 0; j < kScMaxTopk; ++j) tk[j] = j < n_taken ? taken[j] : 0;
+        // the load does not wait for the window test, so the unrolled loads are in flight together
+#pragma unroll 4
+        for (int i = tid; i < n; i += kScSelT) {
+            float d = drow[i];
+            bool free = true;
+#pragma unroll
+            for (int j = 0; j < kScMaxTopk; ++j) {
+                const int gap = i - tk[j];               // both in [0, n_db): no overflow
+                free = free && (j >= n_taken || (gap < 0 ? -gap : gap) > exclusion);
+            }
+            d = d == d ? d : INFINITY;
+            if (free && (d < bd || bi == INT_MAX)) { bd = d; bi = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float od = __shfl_xor(bd, o, kWave);
+            const int oi = __shfl_xor(bi, o, kWave);
+            if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
+        }
+        if (lane == 0) { sd[w] = bd; si[w] = bi; }
+        __syncthreads();
+        bd = sd[0]; bi = si[0];
+        for (int m = 1; m < kScSelT / 64; ++m)
+            if (sd[m] < bd || (sd[m] == bd && si[m] < bi)) { bd = sd[m]; bi = si[m]; }
+        if (bi == INT_MAX) break;                        // the prefix is exhausted, for every thread
+        if (tid == 0) taken[n_taken] = bi;
+        __syncthreads();                                 // `taken` is written, the wave slots are read
+    }
+    // thread j writes slot j after the last round, so no round waits for a record's loads; a slot
+    // that found no candidate gets the record k_sc_select writes without one
+    if (tid < k) {
+        ssf_sc_best o;
+        o.index = -1; o.dist = 1.0f; o.shift = 0; o.reserved = 0;
+        if (tid < n_taken) {
+            const int i = taken[tid];
+            o.index = i; o.dist = drow[i]; o.shift = srow[i];
+        }
+        out[tid] = o;
+    }
+}
+
+// The dist / shift rows of every query against candidates 0 .. n_cols - 1 (n_cols > 0).
+static hipError_t launch_sc_rows(hipStream_t s, int n_query, const float* query, int n_db, int n_cols,
+                                 const float* db, float* dist, int32_t* shift) {
+    static hipError_t once = hipFuncSetAttribute((const void*)k_sc_match,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kScMatchLds);
+    if (once != hipSuccess) return once;
+    ScMatchArgs a;
+    a.query = query; a.db = db; a.dist = dist; a.shift = shift; a.n_db = n_db; a.n_cols = n_cols;
+    a.groups = (n_cols + kScMatchW * kScCpw - 1) / (kScMatchW * kScCpw);
+    kmark(s, "k_sc_match");
+    hipLaunchKernelGGL(k_sc_match, dim3((unsigned)((int64_t)n_query * a.groups)), dim3(kScMatchT), kScMatchLds,
+                       s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_sc_match(hipStream_t s, int n_query, const float* query, int n_db, int n_cols, const float* db,
                            const int32_t* n_eligible, float* dist, int32_t* shift, ssf_sc_best* best) {
     if (n_query <= 0) return hipSuccess;
     if (n_cols > 0) {
-        static hipError_t once = hipFuncSetAttribute((const void*)k_sc_match,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kScMatchLds);
-        if (once != hipSuccess) return once;
-        ScMatchArgs a;
-        a.query = query; a.db = db; a.dist = dist; a.shift = shift; a.n_db = n_db; a.n_cols = n_cols;
-        a.groups = (n_cols + kScMatchW * kScCpw - 1) / (kScMatchW * kScCpw);
-        kmark(s, "k_sc_match");
-        hipLaunchKernelGGL(k_sc_match, dim3((unsigned)((int64_t)n_query * a.groups)), dim3(kScMatchT), kScMatchLds,
-                           s, a);
-        hipError_t e = hipGetLastError();
+        hipError_t e = launch_sc_rows(s, n_query, query, n_db, n_cols, db, dist, shift);
         if (e != hipSuccess) return e;
     }
     kmark(s, "k_sc_select");
     hipLaunchKernelGGL(k_sc_select, dim3(n_query), dim3(kScSelT), 0, s, dist, shift, n_db, n_eligible, best);
+    return hipGetLastError();
+}
+
+hipError_t launch_sc_match_topk(hipStream_t s, int n_query, const float* query, int n_db, int n_cols,
+                                const float* db, const int32_t* n_eligible, float* dist, int32_t* shift, int k,
+                                int exclusion, ssf_sc_best* best) {
+    if (k < 1 || k > kScMaxTopk) return hipErrorInvalidValue;   // `taken` holds kScMaxTopk indices
+    if (n_query <= 0) return hipSuccess;
+    if (n_cols > 0) {
+        hipError_t e = launch_sc_rows(s, n_query, query, n_db, n_cols, db, dist, shift);
+        if (e != hipSuccess) return e;
+    }
+    kmark(s, "k_sc_select_topk");
+    hipLaunchKernelGGL(k_sc_select_topk, dim3(n_query), dim3(kScSelT), 0, s, dist, shift, n_db, n_eligible, k,
+                       exclusion, best);
     return hipGetLastError();
 }
 

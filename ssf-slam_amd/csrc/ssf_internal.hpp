@@ -281,6 +281,11 @@ hipError_t launch_sc_describe(hipStream_t s, int n_clouds, const float* pts, int
                               float max_range, float lidar_height, float* desc);
 hipError_t launch_sc_match(hipStream_t s, int n_query, const float* query, int n_db, int n_cols, const float* db,
                            const int32_t* n_eligible, float* dist, int32_t* shift, ssf_sc_best* best);
+// The same comparison (the same k_sc_match launch) followed by the greedy top-k selection with an
+// exclusion window: best is [n_query, k], k in 1 .. SSF_SC_MAX_TOPK, exclusion >= 0.
+hipError_t launch_sc_match_topk(hipStream_t s, int n_query, const float* query, int n_db, int n_cols,
+                                const float* db, const int32_t* n_eligible, float* dist, int32_t* shift, int k,
+                                int exclusion, ssf_sc_best* best);
 size_t mask_sync_bytes(int n_frames);
 size_t mask_parts_bytes(int n_frames, int G);
 // The Lloyd record / queue buffer of a launch of `total` points in n_frames frames: 8-byte

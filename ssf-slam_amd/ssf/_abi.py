@@ -44,9 +44,12 @@ EXPORTS = [
     "ssf_pgo_robust_default", "ssf_pose_graph_batch_robust",
     "ssf_pgo_lm_default", "ssf_pose_graph_batch_lm",
     "ssf_sc_params_default", "ssf_scan_context_batch", "ssf_scan_context_match",
+    "ssf_scan_context_match_topk",
 ]
-# ssf_scan_context_*: descriptor shape; ssf_sc_best as four 32-bit words per query
+# ssf_scan_context_*: descriptor shape; ssf_sc_best as four 32-bit words per query (and per slot
+# of ssf_scan_context_match_topk, at most SC_MAX_TOPK of them)
 SC_RINGS, SC_SECTORS = 20, 60
+SC_MAX_TOPK = 8
 SC_BEST_STRIDE = 4
 SC_BEST = dict(INDEX=0, DIST=1, SHIFT=2)
 # ssf_subsample_batch: limits and per-frame status codes
@@ -250,6 +253,8 @@ def lib():
     L.ssf_scan_context_batch.restype = i32
     L.ssf_scan_context_match.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.ssf_scan_context_match.restype = i32
+    L.ssf_scan_context_match_topk.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32]
+    L.ssf_scan_context_match_topk.restype = i32
     L.ssf_pn2_last_error.argtypes = []
     L.ssf_pn2_last_error.restype = C.c_char_p
     L.ssf_pn2_furthest_point_sample.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]

@@ -209,6 +209,14 @@ def node_main(exe: str, argv=None):
             det, thr = parse_detector(rospy.get_param("~MAP_DETECTOR"))
             if det != "radius":
                 mkw.update(map_detector=det, map_sc_threshold=thr)
+        # ~MAP_SC_CANDIDATES (not a reference param, default 1): "K[:EXCLUSION]", with the
+        # scan-context detector the K best places are verified by ICP in one batch
+        if rospy.has_param("~MAP_SC_CANDIDATES"):
+            from .scan_context import parse_candidates
+            if "map_detector" not in mkw:
+                raise ValueError("~MAP_SC_CANDIDATES needs ~MAP_DETECTOR scan-context[:THRESHOLD]")
+            k, excl = parse_candidates(rospy.get_param("~MAP_SC_CANDIDATES"))
+            mkw.update(map_sc_candidates=k, map_sc_exclusion=excl)
         node = nodes.MapOptimizationNode(pub, device=a.device, tum_path=path, **mkw)
         if "map_detector" in mkw:
             rospy.Subscriber("/velodyne_points", sensor_msgs.PointCloud2, node.on_scan, queue_size=10)

@@ -20,6 +20,8 @@ goes into the map at its stored key pose (the reference places it at its iSAM2 e
 ``LoopCloser(detector="scan_context")`` replaces the radius search of detectLoopFrameID, which
 finds nothing once the odometry has drifted past its 15 m, by place recognition on Scan Context
 descriptors of the raw scans (``ssf.scan_context``); the default stays the radius.
+With ``sc_candidates=K`` > 1 the K best places are verified by ICP in one batch (``local_maps``,
+``icp_batch``) and the one the geometry likes best closes the loop.
 
 Pose helpers restate pcl/common/eigen.h: getTransformation (roll/pitch/yaw -> affine,
 yaw * pitch * roll) and getTranslationAndEulerAngles.  Key poses are stored in float, as the
@@ -327,6 +329,9 @@ class LoopConstraint:
     correction: np.ndarray       # correctionLidarFrame, 4x4
     shift: int | None = None     # detector="scan_context": the column shift of the match (yaw = shift * 6 deg)
     dist: float | None = None    # and its Scan Context distance
+    # sc_candidates > 1: every candidate ICP verified, in rank order, as
+    # (key_pre, dist, shift, fitness, converged); key_pre / dist / shift above are the chosen one's
+    candidates: list | None = None
 
 
 @dataclass
@@ -373,10 +378,23 @@ class LoopCloser:
     sc: object | None = None
     sc_db: object | None = None                        # ssf.scan_context.ScanContextDB
     sc_match: tuple | None = None                      # (key_pre, dist, shift) of the last accepted match
+    # detector="scan_context", sc_candidates = K > 1: the nearest descriptor is often not the best
+    # place, so the K best places (ScanContextDB.query_topk; no two within
+    # sc_exclusion keyframes of each other, None: search_num, closer ones share a local map) are
+    # verified by ICP in one batch and the best fitness wins.  1: the single nearest, as before
+    sc_candidates: int = 1
+    sc_exclusion: int | None = None
 
     def __post_init__(self):
         if self.detector not in ("radius", "scan_context"):
             raise ValueError(f"LoopCloser: detector is radius or scan_context, not {self.detector!r}")
+        k, e = self.sc_candidates, self.sc_exclusion
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _abi.SC_MAX_TOPK:
+            raise ValueError(f"LoopCloser: sc_candidates is an integer in 1 .. {_abi.SC_MAX_TOPK}, not {k!r}")
+        if e is not None and (isinstance(e, bool) or not isinstance(e, (int, np.integer)) or e < 0):
+            raise ValueError(f"LoopCloser: sc_exclusion is a non-negative integer or None, not {e!r}")
+        if self.detector != "scan_context" and (k != 1 or e is not None):
+            raise ValueError("LoopCloser: sc_candidates and sc_exclusion belong to detector=\"scan_context\"")
         if self.detector == "scan_context":
             from .scan_context import ScanContextDB, sc_params
             if self.sc is None:
@@ -450,6 +468,57 @@ class LoopCloser:
         self.loop_record_index = cur + 2
         return cur, pre
 
+    def _detect_loop_candidates(self):
+        """sc_candidates > 1: detect_loop's gates, then the sc_candidates best places of the
+        eligible prefix (ScanContextDB.query_topk) whose distance is below sc.threshold
+        -> (cur, [(key_pre, dist, shift)] in rank order) or None."""
+        from .scan_context import eligible_prefix
+        cur = len(self.key6d) - 1
+        if cur in self.loop_index:
+            return None
+        n_el = eligible_prefix([k[6] for k in self.key6d[:cur]], self.key6d[cur][6], self.time_gap)
+        if n_el == 0:
+            return None
+        excl = self.search_num if self.sc_exclusion is None else self.sc_exclusion
+        found = self.sc_db.query_topk(self.sc_db.descriptors()[cur], self.sc_candidates, excl, n_el)
+        kept = [c for c in found if c[1] < self.sc.threshold]
+        if not kept:
+            return None
+        self.loop_record_index = cur + 2
+        return cur, kept
+
+    def local_maps(self, items):
+        """local_map for every (key, n) of items in two launches: every keyframe of every map
+        through its own pose in one ssf_transform_clouds_batch, then the concatenated maps through
+        one ssf_voxel_grid_batch (icp_leaf).  -> (maps [total, 4], h_off int64 [len(items) + 1]):
+        map m is maps[h_off[m]:h_off[m + 1]]."""
+        from .map_cloud import pose_rows
+        dev = self.fe.device
+        parts, poses, map_off = [], [], [0]
+        for key, n in items:
+            for k in range(key - n, key + n + 1):
+                if 0 <= k < len(self.key6d):
+                    parts.append(self.key_frames[k])
+                    poses.append(self._T6(k))
+            map_off.append(len(parts))
+        sizes = np.array([int(p.shape[0]) for p in parts], np.int64)
+        part_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        h_off = torch.from_numpy(part_off[map_off])
+        if part_off[-1] == 0:
+            return torch.zeros(0, 4, device=dev), torch.zeros(len(items) + 1, dtype=torch.int64)
+        raw = torch.cat(parts)
+        moved = torch.empty_like(raw)
+        h_part = torch.from_numpy(part_off)
+        d_part = h_part.to(dev)
+        d_T = torch.from_numpy(pose_rows(poses)).to(dev)
+        self.fe._check(_abi.lib().ssf_transform_clouds_batch(
+            self.fe._h, _stream(dev), len(parts), _ptr(raw), _ptr(d_part), C.c_void_p(h_part.data_ptr()),
+            _ptr(d_T), _ptr(moved)), "ssf_transform_clouds_batch")
+        out, cnt = voxel_grid(self.fe, moved, h_off.to(dev), h_off, self.icp_leaf)
+        cnt = cnt.cpu().numpy().astype(np.int64)
+        maps = torch.cat([out[int(h_off[m]):int(h_off[m]) + int(cnt[m])] for m in range(len(items))])
+        return maps, torch.from_numpy(np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64))
+
     def local_map(self, key, n):
         """getLoopLocalMap (:200-218): keyframes key-n..key+n in the map frame, 0.1 m voxels."""
         parts = [transform_cloud(self.key_frames[k], self._T6(k))
@@ -464,6 +533,8 @@ class LoopCloser:
         n = len(self.key6d)
         if n < 5 or n - 1 <= self.loop_record_index:
             return None
+        if self.sc_candidates > 1:
+            return self._add_loop_factor_candidates()
         ids = self.detect_loop()
         if ids is None:
             return None
@@ -482,6 +553,52 @@ class LoopCloser:
             r = icp(self.fe, cur_cloud, pre_cloud)
         if not r["converged"] or r["fitness"] > 0.2:
             return None
+        return self._accept_loop(cur, pre, r)
+
+    def _add_loop_factor_candidates(self):
+        """add_loop_factor with sc_candidates > 1: every candidate verified in one batch
+        (verify_candidates), and among the problems that pass the gates of the single-candidate
+        path the smallest (fitness, rank)."""
+        found = self._detect_loop_candidates()
+        if found is None:
+            return None
+        cur, cands = found
+        tried = self.verify_candidates(cur, cands)
+        ok = [(r["fitness"], j, r) for j, r in tried if r["converged"] and r["fitness"] <= 0.2]
+        if not ok:
+            return None
+        _, j, r = min(ok, key=lambda o: o[:2])
+        self.sc_match = cands[j]
+        c = self._accept_loop(cur, cands[j][0], r)
+        c.candidates = [(*cands[k], q["fitness"], q["converged"]) for k, q in tried]
+        return c
+
+    def verify_candidates(self, cur, cands):
+        """ICP of keyframe cur against every candidate (key_pre, dist, shift) of cands: the local
+        maps of the candidates and the current cloud in one local_maps call, then one icp_batch
+        with one problem per candidate -- the current cloud as every source, the candidate's map
+        as its target, guess = T_pre . Rz(shift . 2 pi / 60) . T_cur^-1 as on the single-candidate
+        path.  -> [(rank, icp result)] for the candidates whose map has at least 1000 points; []
+        when the current cloud has fewer than 300."""
+        maps, h_off = self.local_maps([(c[0], self.search_num) for c in cands] + [(cur, 0)])
+        size = (h_off[1:] - h_off[:-1]).tolist()
+        rank = [j for j in range(len(cands)) if size[j] >= 1000]
+        if size[-1] < 300 or not rank:
+            return []
+        dev = self.fe.device
+        cur_cloud = maps[int(h_off[-2]):int(h_off[-1])]
+        src = cur_cloud.repeat(len(rank), 1)               # ICP moves its source: one copy per problem
+        h_src = torch.arange(len(rank) + 1, dtype=torch.int64) * size[-1]
+        tgt = torch.cat([maps[int(h_off[j]):int(h_off[j + 1])] for j in rank])
+        h_tgt = torch.tensor(np.concatenate([[0], np.cumsum([size[j] for j in rank])]), dtype=torch.int64)
+        inv_cur = np.linalg.inv(self._T6(cur))
+        guess = [self._T6(cands[j][0]) @ get_transformation(0.0, 0.0, 0.0, 0.0, 0.0, cands[j][2] * (2.0 * math.pi / 60.0))
+                 @ inv_cur for j in rank]
+        res = icp_batch(self.fe, src, h_src.to(dev), h_src, tgt, h_tgt.to(dev), h_tgt, guess=guess)
+        return list(zip(rank, res))
+
+    def _accept_loop(self, cur, pre, r):
+        """The rest of addLoopFactor for an ICP result r that passed its gates."""
         corr = r["T"].astype(np.float64)
         self.loop_record_index += 30
         t_correct = corr @ self._T6(cur)

@@ -273,12 +273,15 @@ class MapOptimizationNode:
     loops are found by Scan Context descriptors of the raw scans (ssf.scan_context, DESIGN.md
     §6.12); the node then also takes /velodyne_points (on_scan), pairs each scan with its plane
     cloud by stamp and hands it to the closer; map_sc_threshold: the acceptance distance
-    (default: ssf_sc_params')."""
+    (default: ssf_sc_params'); map_sc_candidates = K > 1: the K best places are verified by ICP in
+    one batch and the best fitness closes the loop (LoopCloser(sc_candidates=)), map_sc_exclusion:
+    no two of them within that many keyframes of each other (default: the closer's search_num)."""
 
     def __init__(self, publish, device=None, frontend: Frontend | None = None,
                  tum_path: str | None = None, optimize: bool = False, map_cloud: bool = False,
                  map_robust=None, map_lm=None, map_iters: int | None = None,
-                 map_detector: str = "radius", map_sc_threshold: float | None = None):
+                 map_detector: str = "radius", map_sc_threshold: float | None = None,
+                 map_sc_candidates: int = 1, map_sc_exclusion: int | None = None):
         from .loop import LoopCloser, get_translation_and_euler_angles, pgo_params  # noqa: F401
         self.publish = publish
         self.fe = frontend or Frontend(64, device=device)
@@ -303,9 +306,13 @@ class MapOptimizationNode:
             raise ValueError(f"map_detector is radius or scan_context, not {map_detector!r}")
         if map_sc_threshold is not None and map_detector != "scan_context":
             raise ValueError("map_sc_threshold is the acceptance distance of map_detector=\"scan_context\"")
+        if (map_sc_candidates != 1 or map_sc_exclusion is not None) and map_detector != "scan_context":
+            raise ValueError("map_sc_candidates and map_sc_exclusion belong to map_detector=\"scan_context\"")
         if map_detector == "scan_context":
             from .scan_context import sc_params
             kw.update(detector="scan_context", sc=sc_params(threshold=map_sc_threshold))
+            if map_sc_candidates != 1 or map_sc_exclusion is not None:
+                kw.update(sc_candidates=map_sc_candidates, sc_exclusion=map_sc_exclusion)
         self.closer = LoopCloser(self.fe, **kw)
         self.scans = []                           # recent /velodyne_points (map_detector="scan_context")
         self.map_cloud = bool(map_cloud)
@@ -422,7 +429,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
                  truncate_results: bool = False, map_optimize: bool = False, map_cloud: bool = False,
                  weights=None, n_points: int = 8192, map_robust=None, map_lm=None,
                  map_iters: int | None = None, map_detector: str = "radius",
-                 map_sc_threshold: float | None = None):
+                 map_sc_threshold: float | None = None, map_sc_candidates: int = 1,
+                 map_sc_exclusion: int | None = None):
     """Replay a DATASET_PATH directory through the node graph of launch/run_<launch>.launch:
       onlyPC: PointCloudOdometry_onlyPC -> frameFeature -> lidarOdometry_onlyPC (registration)
       noSeg:  PointCloudOdometry_noSeg (GMM mask + Kabsch -> /frame_odom1) -> frameFeature ->
@@ -438,7 +446,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
     edges, map_lm: an ssf.loop.pgo_lm step control for those solves, map_iters: their max_iter;
     all three need map_optimize; map_detector="scan_context": its loops are found by Scan Context
     descriptors of the /velodyne_points scans instead of the radius search, map_sc_threshold the
-    acceptance distance).  Stamps are synthetic and monotone (frame k
+    acceptance distance, map_sc_candidates / map_sc_exclusion the places it verifies by ICP per
+    keyframe and how many keyframes apart they lie at least).  Stamps are synthetic and monotone (frame k
     at k / rate_hz; the reference uses wall-clock ros::Time::now()).  The /frame_odom2 poses are
     appended to `tum_path` as TUM lines (like the reference, an existing file is extended unless
     truncate_results=True).
@@ -465,6 +474,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
         raise ValueError("map_detector chooses mapOptmization's loop detector: pass map_tum_path")
     if map_sc_threshold is not None and map_detector != "scan_context":
         raise ValueError("map_sc_threshold is the acceptance distance of map_detector=\"scan_context\"")
+    if (map_sc_candidates != 1 or map_sc_exclusion is not None) and map_detector != "scan_context":
+        raise ValueError("map_sc_candidates and map_sc_exclusion belong to map_detector=\"scan_context\"")
     src_mode, odo_kind, keys = LAUNCH_GRAPHS[launch][:3]
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     bus = Bus()
@@ -516,6 +527,8 @@ def run_sequence(root: str, tum_path: str | None = None, n_rows: int = 64, devic
             mkw["map_iters"] = map_iters
         if map_detector != "radius":
             mkw.update(map_detector=map_detector, map_sc_threshold=map_sc_threshold)
+        if map_sc_candidates != 1 or map_sc_exclusion is not None:
+            mkw.update(map_sc_candidates=map_sc_candidates, map_sc_exclusion=map_sc_exclusion)
         mo = MapOptimizationNode(bus.publish, device=dev, tum_path=map_tum_path or None, **mkw)
         bus.subscribe("/plane_frame_cloud2", mo.on_plane_cloud)
         bus.subscribe("/frame_odom2", mo.on_odom)

@@ -4,7 +4,8 @@ sequence through the device front-end as one of the reference's launch files wir
 run_Seg_ActiveSceneFlow.launch with --weights; ssf.nodes.LAUNCH_GRAPHS) and append
 /frame_odom2 to a TUM trajectory (optionally with mapOptmization's loop closure, with
 --map-cloud its accumulated map cloud saved as an npy file, and with --map-detector scan-context
-its loops found by Scan Context descriptors instead of the radius search)."""
+its loops found by Scan Context descriptors instead of the radius search, with
+--map-sc-candidates K the K best places verified by ICP in one batch)."""
 from __future__ import annotations
 
 import argparse
@@ -50,6 +51,11 @@ def main(argv=None):
                          "reference's 15 m search over the estimated key positions, scan-context compares "
                          "Scan Context descriptors of the raw scans on the GPU and also finds a loop "
                          "after the odometry has drifted; THRESHOLD the acceptance distance (default 0.13)")
+    ap.add_argument("--map-sc-candidates", default=None, metavar="K[:EXCLUSION]",
+                    help="with --map-detector scan-context: verify the K (1 .. 8) best places by ICP in one "
+                         "batch and close the loop at the one with the best fitness, instead of trying "
+                         "only the nearest descriptor; no two places lie within EXCLUSION keyframes of "
+                         "each other (default 10, the half-width of a local map)")
     ap.add_argument("--weights", default=None, metavar="FILE",
                     help="the ActiveSceneFlow launches: TFlow checkpoint (a state dict with the "
                          "reference's keys, a DataParallel `module.` prefix accepted)")
@@ -101,6 +107,15 @@ def main(argv=None):
         kw["map_detector"] = detector
         if thr is not None:
             kw["map_sc_threshold"] = thr
+    if a.map_sc_candidates is not None:
+        if detector != "scan_context":
+            ap.error("--map-sc-candidates needs --map-detector scan-context[:THRESHOLD]: the candidates are "
+                     "those of the Scan Context search")
+        from .scan_context import parse_candidates
+        try:
+            kw["map_sc_candidates"], kw["map_sc_exclusion"] = parse_candidates(a.map_sc_candidates)
+        except ValueError as e:
+            ap.error(f"--map-sc-candidates: {e}")
     torch.cuda.set_device(a.device)
     from .nodes import ASF_LAUNCHES
     if a.launch in ASF_LAUNCHES:
@@ -135,6 +150,11 @@ def main(argv=None):
                 threshold=kw.get("map_sc_threshold", 0.13),
                 matches=[{"key_cur": c.key_cur, "key_pre": c.key_pre, "dist": c.dist, "shift": c.shift}
                          for c in res["loops"]])
+            if a.map_sc_candidates is not None:      # per closed loop: the places ICP was tried at
+                extra["map_detector"].update(
+                    candidates=kw["map_sc_candidates"], exclusion=kw["map_sc_exclusion"],
+                    candidates_tried=[[{"key_pre": k, "dist": d, "shift": s, "fitness": f, "converged": ok}
+                                       for k, d, s, f, ok in (c.candidates or [])] for c in res["loops"]])
     if res.get("flow_metrics"):                     # the dataset carries gt: the mean of each metric
         fm = res["flow_metrics"]
         extra["flow_metrics"] = {k: sum(m[k] for m in fm) / len(fm) for k in fm[0]}

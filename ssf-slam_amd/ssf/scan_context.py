@@ -5,7 +5,9 @@ include/ssf_frontend.h).
 ``describe`` <- ssf_scan_context_batch: the 20 ring x 60 sector descriptor of ragged clouds in
 the sensor frame.  ``match`` <- ssf_scan_context_match: every query against every database
 descriptor at all 60 column shifts, and per query the nearest candidate of an eligible prefix of
-the database in the order (dist, index).  ``ScanContextDB`` keeps the descriptors of a sequence's
+the database in the order (dist, index).  ``match_topk`` <- ssf_scan_context_match_topk: per
+query the k best candidates whose indices lie more than an exclusion window apart, for a caller
+that verifies several places (LoopCloser(sc_candidates=...)).  ``ScanContextDB`` keeps the descriptors of a sequence's
 keyframes in one growing device buffer.  The CPU implementations' ring-key kd-tree and sector-key
 coarse alignment are not built: the exhaustive search replaces both.  There is no host path.
 """
@@ -62,6 +64,22 @@ def parse_detector(text):
         return kind, float(thr)
     except ValueError:
         raise ValueError(f"detector {text!r}: THRESHOLD must be a number") from None
+
+
+def parse_candidates(text):
+    """"K[:EXCLUSION]" (the --map-sc-candidates command-line form) -> (K, exclusion or None):
+    K in 1 .. 8 places verified per keyframe, no two within EXCLUSION keyframes of each other."""
+    k, sep, excl = str(text).partition(":")
+    try:
+        k = int(k)
+        excl = int(excl) if sep else None
+    except ValueError:
+        raise ValueError(f"candidates {text!r}: K[:EXCLUSION], two integers") from None
+    if not 1 <= k <= _abi.SC_MAX_TOPK:
+        raise ValueError(f"candidates {text!r}: K outside 1 .. {_abi.SC_MAX_TOPK}")
+    if excl is not None and excl < 0:
+        raise ValueError(f"candidates {text!r}: EXCLUSION is negative")
+    return k, excl
 
 
 def eligible_prefix(stamps, cur_stamp, time_gap) -> int:
@@ -134,6 +152,53 @@ def match(fe: Frontend, queries: torch.Tensor, db: torch.Tensor, n_eligible, ful
     return out + (dist, shift) if full else out
 
 
+def _check_topk(k, exclusion, what):
+    """k in 1 .. SC_MAX_TOPK and exclusion >= 0, both integers -> (k, exclusion)."""
+    for name, v in (("k", k), ("exclusion", exclusion)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: {name} is an integer, not {v!r}")
+    if not 1 <= k <= _abi.SC_MAX_TOPK:
+        raise ValueError(f"{what}: k outside 1 .. {_abi.SC_MAX_TOPK}")
+    if exclusion < 0:
+        raise ValueError(f"{what}: exclusion is negative")
+    return int(k), min(int(exclusion), 2 ** 31 - 1)
+
+
+def match_topk(fe: Frontend, queries: torch.Tensor, db: torch.Tensor, n_eligible, k: int, exclusion: int = 0,
+               full: bool = False):
+    """``match`` with the k best places per query instead of the one best candidate
+    (ssf_scan_context_match_topk): the candidates 0 .. n_eligible - 1 are walked in the order
+    (dist, index) and one is taken when its index differs by more than `exclusion` from every index
+    already taken, until k are taken or none is left.  k in 1 .. 8, exclusion >= 0 (ValueError
+    before any device call).  -> (idx [Q, k] int32, dist [Q, k] float32, shift [Q, k] int32) on the
+    device, in rank order, an unfilled slot (-1, 1.0, 0); column 0 is ``match``'s result bit for
+    bit.  full=True: also (dist [Q, N], shift [Q, N]) of every pair."""
+    k, exclusion = _check_topk(k, exclusion, "scan_context.match_topk")
+    queries = _check_desc(queries, "scan_context.match_topk: queries")
+    db = _check_desc(db, "scan_context.match_topk: db")
+    Q, N = int(queries.shape[0]), int(db.shape[0])
+    ne = np.asarray(n_eligible, np.int64).reshape(-1)
+    if ne.size == 1:
+        ne = np.repeat(ne, Q)
+    if ne.size != Q:
+        raise ValueError(f"scan_context.match_topk: {ne.size} n_eligible for {Q} queries")
+    if Q and (ne.min() < 0 or ne.max() > N):
+        raise ValueError(f"scan_context.match_topk: n_eligible outside 0 .. {N}")
+    h_ne = torch.from_numpy(ne.astype(np.int32))
+    dev = queries.device
+    d_ne = h_ne.to(dev)
+    best = torch.empty((Q, k, _abi.SC_BEST_STRIDE), dtype=torch.int32, device=dev)
+    dist = torch.empty((Q, N), dtype=torch.float32, device=dev) if full else None
+    shift = torch.empty((Q, N), dtype=torch.int32, device=dev) if full else None
+    fe._check(_abi.lib().ssf_scan_context_match_topk(fe._h, _stream(fe.device), Q, _ptr(queries), N,
+                                                     _ptr(db) if N else None, _ptr(d_ne),
+                                                     C.c_void_p(h_ne.data_ptr()), _ptr(dist), _ptr(shift),
+                                                     _ptr(best), k, exclusion), "ssf_scan_context_match_topk")
+    out = (best[:, :, _abi.SC_BEST["INDEX"]], best[:, :, _abi.SC_BEST["DIST"]].view(torch.float32),
+           best[:, :, _abi.SC_BEST["SHIFT"]])
+    return out + (dist, shift) if full else out
+
+
 class ScanContextDB:
     """The descriptors of a sequence's keyframes in one device buffer [capacity, 20, 60]; the
     capacity doubles with the contents kept (as ssf.MapCloud's store does), between growths
@@ -186,3 +251,17 @@ class ScanContextDB:
         if not one:
             return idx, dist, shift
         return int(idx[0]), float(dist[0]), int(shift[0])
+
+    def query_topk(self, desc: torch.Tensor, k: int, exclusion: int = 0, n_eligible=None):
+        """A descriptor [20, 60] against the stored prefix -> the at most k places ``match_topk``
+        takes, a list of (idx, dist, shift) tuples of Python numbers in rank order (unfilled
+        slots dropped).  Several descriptors [Q, 20, 60] -> the three [Q, k] device tensors."""
+        k, exclusion = _check_topk(k, exclusion, "ScanContextDB.query_topk")
+        n_el = self.n if n_eligible is None else n_eligible
+        one = desc.dim() == 2
+        q = desc.unsqueeze(0) if one else desc
+        idx, dist, shift = match_topk(self.fe, q, self.descriptors(), n_el, k, exclusion)
+        if not one:
+            return idx, dist, shift
+        rows = zip(idx[0].tolist(), dist[0].tolist(), shift[0].tolist())
+        return [(i, d, s) for i, d, s in rows if i >= 0]

@@ -11,6 +11,11 @@
     has no detector, so that composition is the comparison; its distances are compared with the
     kernel's (the largest difference is recorded, nothing is asserted).
 
+--topk writes profiles/sc_topk_bench.json instead: (c) ssf_scan_context_match against
+ssf_scan_context_match_topk at k = 1, 4 and 8, selection only, and (d) the batched verification of
+four candidates (LoopCloser.verify_candidates) against four sequential local_map + icp pairs on the
+revisit scene of the loop tests.
+
 No threshold is set.  HIP events around each Python call on the current stream, one synchronise per
 sample; the variants alternate in one process; warm-up first, median of --runs samples (>= 20)."""
 import argparse
@@ -57,14 +62,120 @@ def torch_match(torch, q, db):
     return dist.argmin(dim=1), dist, shift
 
 
+def revisit_closer(torch, ssf, fe, dev, k_cand, exclusion):
+    """The revisit scene of the loop tests (30 synthetic frames forward, n_az = 600; the plane
+    clouds from the device's own feature stage) in a LoopCloser, the revisit of frame 0 (yawed by
+    180 degrees, 40 m of drift) as its last keyframe, and k_cand candidates for it from
+    query_topk with no threshold applied (a window of `exclusion` keyframes: the scene has some
+    20 keyframes, too few for k_cand places 11 apart) -> (closer, cur, candidates)."""
+    from ssf import loop, scan_context as sc, synth
+    scene = synth.Scene(0)
+    scans = [synth.scan(0, k, n_az=600, scene=scene)["pos1"] for k in range(30)]
+    turned = scans[0].clone()
+    turned[:, :2] = -turned[:, :2]
+    scans.append(turned)
+    R0, p0 = synth.ego_pose(0, 0)
+    T0 = np.eye(4); T0[:3, :3] = R0.numpy(); T0[:3, 3] = p0.numpy()
+    pts = torch.cat(scans).to(dev)
+    off, h_off = ssf.frame_offsets([s.shape[0] for s in scans], dev)
+    pb = fe.extract_planes_batch(pts, off, h_off)
+    lc = loop.LoopCloser(fe, detector="scan_context", sc=sc.sc_params(threshold=0.0), sc_candidates=k_cand)
+    for i in range(31):
+        R, p = synth.ego_pose(0, i % 30)
+        T = np.eye(4); T[:3, :3] = R.numpy(); T[:3, 3] = p.numpy()
+        T = np.linalg.inv(T0) @ T
+        if i == 30:
+            T = T @ loop.get_transformation(0, 0, 0, 0, 0, np.pi)
+            T[1, 3] += 40.0
+        yaw = np.arctan2(T[1, 0], T[0, 0])
+        lc.process(pb.frame(i).clone(), (0.0, 0.0, np.sin(yaw / 2), np.cos(yaw / 2)), T[:3, 3],
+                   0.1 * i + (30.0 if i == 30 else 0.0), scan=scans[i].to(dev))   # threshold 0: nothing is accepted
+    cur = len(lc.key6d) - 1
+    cands = lc.sc_db.query_topk(lc.sc_db.descriptors()[cur], k_cand, exclusion, cur)
+    return lc, cur, cands
+
+
+def topk(a):
+    """--topk: (a) ssf_scan_context_match against ssf_scan_context_match_topk at k = 1, 4 and 8,
+    selection only, 8192 descriptors, 1 and 64 queries; (b) the verification of K = 4 candidates
+    on the revisit scene in one batch (LoopCloser.verify_candidates: local_maps + one icp_batch)
+    against four sequential local_map + icp pairs.  The same protocol as the default mode."""
+    import math
+    import torch
+    import ssf
+    from ssf import loop, scan_context as sc
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(20261021)
+    fe = ssf.Frontend(64, device=0)
+    with torch.no_grad():
+        m = 3000
+        r, phi = torch.rand((N_DB + 64) * m, device=dev) * 80.0, torch.rand((N_DB + 64) * m, device=dev) * (2 * np.pi)
+        pts = torch.stack([r * torch.cos(phi), r * torch.sin(phi), torch.rand_like(r) * 10.0 - 2.0], dim=1).contiguous()
+        o2, h2 = ssf.frame_offsets([m] * (N_DB + 64), dev)
+        descs = sc.describe(fe, pts, o2, h2)
+        del pts, r, phi
+        db, queries = descs[:N_DB].contiguous(), descs[N_DB:].contiguous()
+        select = {}
+        for Q in (1, 64):
+            q = queries[:Q].contiguous()
+            res = timed(torch, (("match", lambda: sc.match(fe, q, db, N_DB)),
+                                ("topk_k1", lambda: sc.match_topk(fe, q, db, N_DB, 1, 10)),
+                                ("topk_k4", lambda: sc.match_topk(fe, q, db, N_DB, 4, 10)),
+                                ("topk_k8", lambda: sc.match_topk(fe, q, db, N_DB, 8, 10))), a.warmup, a.runs)
+            for k in (1, 4, 8):
+                res[f"topk_k{k}_over_match"] = res[f"topk_k{k}"]["median_ms"] / res["match"]["median_ms"]
+            one = sc.match(fe, q, db, N_DB)
+            top = sc.match_topk(fe, q, db, N_DB, 8, 10)
+            res["slot0_equals_match"] = bool(all(torch.equal(x, y[:, 0]) for x, y in zip(one, top)))
+            select[f"q{Q}"] = dict(queries=Q, exclusion=10, **res)
+            print(json.dumps(select[f"q{Q}"]), flush=True)
+        lc, cur, cands = revisit_closer(torch, ssf, fe, dev, 4, 4)
+        inv_cur = np.linalg.inv(lc._T6(cur))
+
+        def sequential():
+            out = []
+            for pre, _, shift in cands:
+                cur_cloud, pre_cloud = lc.local_map(cur, 0), lc.local_map(pre, lc.search_num)
+                g = lc._T6(pre) @ loop.get_transformation(0.0, 0.0, 0.0, 0.0, 0.0, shift * (2.0 * math.pi / 60.0)) @ inv_cur
+                out.append(loop.icp(fe, cur_cloud, pre_cloud, guess=g))
+            return out
+        verify = timed(torch, (("batched", lambda: lc.verify_candidates(cur, cands)), ("sequential", sequential)),
+                       a.warmup, a.runs)
+        verify["sequential_over_batched"] = verify["sequential"]["median_ms"] / verify["batched"]["median_ms"]
+        bat, seq = lc.verify_candidates(cur, cands), sequential()
+        verify["candidates"] = [dict(key_pre=cands[j][0], dist=cands[j][1], shift=cands[j][2], fitness_batched=b["fitness"],
+                                     iterations_batched=b["iterations"], fitness_sequential=seq[j]["fitness"],
+                                     iterations_sequential=seq[j]["iterations"]) for j, b in bat]
+        verify["exclusion"] = 4
+        verify["keyframes"] = len(lc.key6d)
+        print(json.dumps(verify), flush=True)
+    props = torch.cuda.get_device_properties(0)
+    out = dict(tool="tools/bench_sc.py --topk", device=props.name, arch=props.gcnArchName, runs=a.runs, warmup=a.warmup,
+               timing="HIP events around the Python call (its small host copies and allocations included; "
+                      "ssf_icp_batch is synchronous), one sync per sample, variants alternating in one process",
+               unmeasured="the kernels alone (no kernel-trace run), any counter, K other than 4 for the verification",
+               select=dict(database=N_DB, **select), verify=dict(k=4, **verify))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "sc_bench.json"))
+    ap.add_argument("--topk", action="store_true",
+                    help="time the top-K selection and the batched candidate verification instead "
+                         "(default --out: profiles/sc_topk_bench.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.runs < 20:
         ap.error("--runs must be at least 20")
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "sc_topk_bench.json" if a.topk else "sc_bench.json")
+    if a.topk:
+        return topk(a)
     import torch
     import ssf
     from ssf import scan_context as sc
