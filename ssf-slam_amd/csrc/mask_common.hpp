@@ -110,13 +110,37 @@ SSF_DEV void load_raw(const T* __restrict__ P, const T* __restrict__ Fl, int64_t
     r[3] = P[3 * i];  r[4] = P[3 * i + 1];  r[5] = P[3 * i + 2];
 }
 
+// Cache policy of the point streams.  A frame's [flow, xyz] is 2.88 MB and
+// hundreds of frames are in flight, so no point byte read by a loop over a whole part is found
+// in a cache again: those loops (for_points_deep, for_point_pairs, the two k-means++ streams)
+// read with the non-temporal policy, global_load ... nt, and leave the L2 to the bytes that are
+// re-used -- the Lloyd records, the relabel queues and the gathers of relabelled points, which
+// stay at the default policy like every single-point read (each measured with nt and slower or
+// equal).  SSF_NT_POINTS=0 builds the default-policy loads for an A/B.
+#ifndef SSF_NT_POINTS
+#define SSF_NT_POINTS 1
+#endif
+#if SSF_NT_POINTS
+#define SSF_STREAM_LOAD(p) __builtin_nontemporal_load(p)
+#else
+#define SSF_STREAM_LOAD(p) (*(p))
+#endif
+
+// load_raw for a loop that streams a whole part
+template <class T>
+SSF_DEV void load_raw_stream(const T* __restrict__ P, const T* __restrict__ Fl, int64_t i, T r[6]) {
+    r[0] = SSF_STREAM_LOAD(&Fl[3 * i]); r[1] = SSF_STREAM_LOAD(&Fl[3 * i + 1]); r[2] = SSF_STREAM_LOAD(&Fl[3 * i + 2]);
+    r[3] = SSF_STREAM_LOAD(&P[3 * i]);  r[4] = SSF_STREAM_LOAD(&P[3 * i + 1]);  r[5] = SSF_STREAM_LOAD(&P[3 * i + 2]);
+}
+
 // three consecutive Ts at byte offset o (< 2^32) of a wave-uniform base: the global_load's SGPR
 // base + 32-bit VGPR offset form, so the clamped index costs a min and a multiply per point
-// instead of 64-bit compares, selects and address arithmetic
+// instead of 64-bit compares, selects and address arithmetic.  Only the whole-part streams use
+// it, so it reads with their policy (one global_load_dwordx3 ... nt for float).
 template <class Ts>
 SSF_DEV void load3_off(const Ts* __restrict__ base, uint32_t o, Ts r[3]) {
     const Ts* p = reinterpret_cast<const Ts*>(reinterpret_cast<const char*>(base) + o);
-    r[0] = p[0]; r[1] = p[1]; r[2] = p[2];
+    r[0] = SSF_STREAM_LOAD(&p[0]); r[1] = SSF_STREAM_LOAD(&p[1]); r[2] = SSF_STREAM_LOAD(&p[2]);
 }
 
 // A wave-uniform LDS value moved to SGPRs: the per-point loops keep their VGPRs for the point

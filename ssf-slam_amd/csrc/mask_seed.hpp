@@ -118,7 +118,7 @@ SSF_DEV bool mask_kmeanspp(MaskCtx<T>& C, const MaskLds& L, const double* __rest
     T kb[kKppDeep][6];
     if (ws < we) {
 #pragma unroll
-        for (int k = 0; k < kKppDeep; ++k) load_raw(P, Fl, min(ws + 64 * k + lane, wlast), kb[k]);
+        for (int k = 0; k < kKppDeep; ++k) load_raw_stream(P, Fl, min(ws + 64 * k + lane, wlast), kb[k]);
     }
     for (int64_t b0 = ws; b0 < we; b0 += 64 * kKppDeep)
 #pragma unroll
@@ -129,7 +129,7 @@ SSF_DEV bool mask_kmeanspp(MaskCtx<T>& C, const MaskLds& L, const double* __rest
         double x[6];
 #pragma unroll
         for (int d = 0; d < 6; ++d) x[d] = (double)kb[k][d];
-        load_raw(P, Fl, min(i + 64 * kKppDeep, wlast), kb[k]);
+        load_raw_stream(P, Fl, min(i + 64 * kKppDeep, wlast), kb[k]);
         const double d = i < we ? dist0x(x) : 0.0;
         wsum += d;
         if (use_blocks) {
@@ -228,7 +228,7 @@ SSF_DEV bool mask_kmeanspp(MaskCtx<T>& C, const MaskLds& L, const double* __rest
     double cp[2] = {0.0, 0.0};
     if (ws < we) {
 #pragma unroll
-        for (int k = 0; k < kKppDeep; ++k) load_raw(P, Fl, min(ws + 64 * k + lane, wlast), kb[k]);
+        for (int k = 0; k < kKppDeep; ++k) load_raw_stream(P, Fl, min(ws + 64 * k + lane, wlast), kb[k]);
     }
     for (int64_t b0 = ws; b0 < we; b0 += 64 * kKppDeep)
 #pragma unroll
@@ -239,7 +239,7 @@ SSF_DEV bool mask_kmeanspp(MaskCtx<T>& C, const MaskLds& L, const double* __rest
         double x[6];
 #pragma unroll
         for (int d = 0; d < 6; ++d) x[d] = (double)kb[k][d];
-        load_raw(P, Fl, min(i + 64 * kKppDeep, wlast), kb[k]);
+        load_raw_stream(P, Fl, min(i + 64 * kKppDeep, wlast), kb[k]);
         if (i < we) {
             double xs = 0.0, dt0 = 0.0, dt1 = 0.0, dtc = 0.0;
 #pragma unroll
