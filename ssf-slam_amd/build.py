@@ -13,13 +13,15 @@ OUT_DIR = os.path.join(HERE, "ssf", "_lib")
 OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libssf_frontend.so")
 SYNTH_LIB = os.path.join(OUT_DIR, "libssf_synth.so")
-SOURCES = ["abi.hip", "features.hip", "ring_table.hip", "feat_bin.hip", "feat_chunk.hip", "feat_wave.hip",
+SOURCES = ["abi_core.hip", "abi_features.hip", "abi_register.hip", "abi_mask.hip", "abi_map.hip",
+           "features.hip", "ring_table.hip", "feat_bin.hip", "feat_chunk.hip", "feat_wave.hip",
            "feat_select.hip", "plane_table.hip", "associate.hip", "edges.hip", "solve.hip", "mask_pose.hip",
            "mask_pose_f64.hip", "kabsch_f32.hip", "subsample.hip", "loop.hip", "pose_graph.hip", "pointnet2.hip", "cost_volume.hip",
            "scan_context.hip"]
 # sources that include another source file
 SRC_DEPS = {"mask_pose_f64.hip": ["mask_pose.hip"]}
-HEADERS = ["ssf_device.hpp", "ssf_internal.hpp", "feat_common.hpp", "reg_knn.hpp", "reg_strips.hpp", "svd3.hpp", "mlp_tile.hpp",
+HEADERS = ["ssf_device.hpp", "ssf_internal.hpp", "abi_ctx.hpp", "numpy_rng.hpp",
+           "feat_common.hpp", "reg_knn.hpp", "reg_strips.hpp", "svd3.hpp", "mlp_tile.hpp",
            "mask_common.hpp", "mask_exchange.hpp", "mask_gmm.hpp", "mask_kabsch.hpp", "mask_seed.hpp", "mask_lloyd.hpp",
            "mask_em.hpp", "mask_final.hpp",
            "pgo_common.hpp", "pgo_linearise.hpp", "pgo_tridiag.hpp", "pgo_capacitance.hpp", "pgo_step.hpp",

@@ -152,36 +152,26 @@ __global__ __launch_bounds__(kMaskThreads) void k_mask_pose(
 }
 
 template <class T>
-static hipError_t launch_mask_pose_t(hipStream_t s, int n_frames, const T* pts, const T* flow,
-                                     const int64_t* frame_off, int mode, const uint8_t* mask_in,
-                                     const double* draws, uint2* lloyd_rec, int reflection,
-                                     uint8_t* bg_mask, double* out, int G, int slots,
-                                     uint32_t* sync, double* parts, const int32_t* order, int queue) {
+hipError_t launch_mask_pose(hipStream_t s, int n_frames, const MaskPlan& plan, const MaskArgs<T>& a) {
     if (n_frames <= 0) return hipSuccess;
-    if (mode != SSF_MASK_GMM || G < 1 || !sync || !parts) G = 1;
-    if (G > kMaxSplit) G = kMaxSplit;
-    int grid = n_frames;
-    // the frame queue (G == 1): at most `queue` work-groups, each taking frame tickets in order
-    const bool tickets = G > 1 || (queue > 0 && sync && queue < n_frames);
-    if (tickets) {
+    if (plan.tickets) {
         // zero the ticket and arrival counters (16-byte multiple, from the allocation start)
         const size_t zb = (mask_sync_bytes(n_frames) + 15) & ~(size_t)15;
-        hipError_t e = hipMemsetAsync(sync, 0, zb, s);
+        hipError_t e = hipMemsetAsync(a.sync, 0, zb, s);
         if (e != hipSuccess) return e;
-        const int64_t want = (int64_t)n_frames * G;
-        const int cap = G > 1 ? slots : queue;
-        grid = (int)(cap > 0 && want > cap ? cap : want);
     }
     kmark(s, sizeof(T) == 8 ? "k_mask_pose_f64" : "k_mask_pose");
-    hipLaunchKernelGGL(k_mask_pose<T>, dim3(grid), dim3(kMaskThreads), 0, s, pts, flow, frame_off,
-                       mode, mask_in, draws, lloyd_rec, reflection, bg_mask, out, n_frames, G, sync,
-                       parts, order, tickets ? 1 : 0);
+    hipLaunchKernelGGL(k_mask_pose<T>, dim3(plan.grid), dim3(kMaskThreads), 0, s, a.pts, a.flow, a.frame_off,
+                       a.mode, a.mask_in, a.draws, a.lloyd_rec, a.reflection, a.bg_mask, a.out, n_frames, plan.G,
+                       a.sync, a.parts, a.order, plan.tickets ? 1 : 0);
     return hipGetLastError();
 }
 
 // One storage type per translation unit (mask_pose_f64.hip compiles this file again with
 // SSF_MASK_F64_TU), so the float kernel's code generation does not depend on the f64 variant.
 #ifndef SSF_MASK_F64_TU
+template hipError_t launch_mask_pose<float>(hipStream_t, int, const MaskPlan&, const MaskArgs<float>&);
+
 int mask_pose_slots(int device) {
     int cus = 0, per = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
@@ -200,25 +190,24 @@ size_t mask_rec_bytes(int64_t total, int n_frames) {
            sizeof(uint32_t) * (size_t)lloyd_queue_count(total, n_frames);
 }
 
-hipError_t launch_mask_pose(hipStream_t s, int n_frames, const float* pts, const float* flow,
-                            const int64_t* frame_off, int mode, const uint8_t* mask_in,
-                            const double* draws, uint2* lloyd_rec, int reflection, uint8_t* bg_mask,
-                            double* out, int G, int slots, uint32_t* sync, double* parts,
-                            const int32_t* order, int queue) {
-    return launch_mask_pose_t(s, n_frames, pts, flow, frame_off, mode, mask_in, draws, lloyd_rec,
-                              reflection, bg_mask, out, G, slots, sync, parts, order, queue);
+MaskPlan mask_plan(int n_frames, int64_t total, int mode, int split, int slots, int queue) {
+    MaskPlan p{};
+    p.G = split > 0 ? split : slots > 0 ? slots / n_frames : 1;
+    p.G = std::max(1, std::min(p.G, kMaxSplit));
+    if (mode != SSF_MASK_GMM) p.G = 1;
+    p.queue = p.G == 1 && queue > 0 && queue < n_frames ? queue : 0;
+    p.tickets = p.G > 1 || p.queue > 0;
+    const int64_t want = (int64_t)n_frames * p.G;       // with tickets: at most cap work-groups
+    const int cap = p.G > 1 ? slots : p.queue;
+    p.grid = (int)(p.tickets && cap > 0 && want > cap ? cap : want);
+    p.draws_bytes = sizeof(double) * 3 * (size_t)n_frames;
+    p.rec_bytes = mode == SSF_MASK_GMM ? mask_rec_bytes(total, n_frames) : 0;
+    p.sync_bytes = p.tickets ? mask_sync_bytes(n_frames) + 16 : 0;
+    p.parts_bytes = mask_parts_bytes(n_frames, p.G);
+    return p;
 }
-
 #else
-hipError_t launch_mask_pose(hipStream_t s, int n_frames, const double* pts, const double* flow,
-                            const int64_t* frame_off, int mode, const uint8_t* mask_in,
-                            const double* draws, uint2* lloyd_rec, int reflection, uint8_t* bg_mask,
-                            double* out, int G, int slots, uint32_t* sync, double* parts,
-                            const int32_t* order, int queue) {
-    return launch_mask_pose_t(s, n_frames, pts, flow, frame_off, mode, mask_in, draws, lloyd_rec,
-                              reflection, bg_mask, out, G, slots, sync, parts, order, queue);
-}
-
+template hipError_t launch_mask_pose<double>(hipStream_t, int, const MaskPlan&, const MaskArgs<double>&);
 #endif
 
 }  // namespace ssf

@@ -3,16 +3,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 
 #include "../../include/ssf_frontend.h"
 
 namespace ssf {
 
-// Device scratch owned by a context: grown on demand, never shrunk.
+// Device scratch owned by a context: grown on demand, never shrunk, released with its owner.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t need) {
         if (need <= bytes) return hipSuccess;
         if (p) {
@@ -207,6 +212,10 @@ struct RegScratch {
     int32_t* ncompact;        // >= n_pairs: let the lane-mode association hand the solve
                               // compacted records; null: records in query order
 };
+// bytes of corr, and of nnv with ncompact behind it (ncompact = nnv + reg_queries(total))
+inline size_t reg_queries(int64_t total) { return (size_t)std::max<int64_t>(total, 1); }
+inline size_t reg_corr_bytes(int64_t total) { return sizeof(CorrRec) * reg_queries(total); }
+inline size_t reg_cidx_bytes(int64_t total, int n_pairs) { return sizeof(int32_t) * (reg_queries(total) + (size_t)n_pairs); }
 struct RegisterArgs {
     RegFrames last;
     RegTable table;
@@ -244,22 +253,46 @@ hipError_t launch_edge_table(hipStream_t s, const ssf_edge_config& ec, int n_fra
 hipError_t launch_accumulate(hipStream_t s, int n, const double* rel, const double* start,
                              double* abs_out);
 
-// ---- launchers (mask_pose.hip) ----
-// G > 1 cuts every frame into G parts on G work-groups (sync: ticket + per-frame arrival
-// counters, mask_sync_bytes; parts: exchange slots, mask_parts_bytes); slots = resident
-// work-groups of k_mask_pose on the device (mask_pose_slots).  order (nullable): the dispatch
-// order of the frames (a device permutation); queue > 0 (G == 1): at most `queue` work-groups
-// taking frame tickets in order (the frame queue; sync holds the ticket).
-hipError_t launch_mask_pose(hipStream_t s, int n_frames, const float* pts, const float* flow,
-                            const int64_t* frame_off, int mode, const uint8_t* mask_in,
-                            const double* draws, uint2* lloyd_rec, int reflection, uint8_t* bg_mask,
-                            double* out, int G, int slots, uint32_t* sync, double* parts,
-                            const int32_t* order = nullptr, int queue = 0);
-hipError_t launch_mask_pose(hipStream_t s, int n_frames, const double* pts, const double* flow,
-                            const int64_t* frame_off, int mode, const uint8_t* mask_in,
-                            const double* draws, uint2* lloyd_rec, int reflection, uint8_t* bg_mask,
-                            double* out, int G, int slots, uint32_t* sync, double* parts,
-                            const int32_t* order = nullptr, int queue = 0);
+// ---- launcher (mask_pose.hip) ----
+// How a mask launch of n_frames frames (`total` points) runs and what scratch it needs: host
+// arithmetic only.  G > 1 cuts every frame into G parts on G work-groups (sync: ticket +
+// per-frame arrival counters; parts: exchange slots).  split: parts per frame, 0 = automatic,
+// as many as keep the `slots` resident work-groups of k_mask_pose (mask_pose_slots) busy; a fixed
+// split is honoured as set (frames x G may exceed the slots: work-groups then take several
+// tickets) and its exchange scratch grows with it (frames x G x 104 KiB, see
+// ssf_set_mask_split).  Only the GMM fit splits.  queue > 0 (G == 1, fewer than n_frames): at
+// most `queue` work-groups taking frame tickets in order (the frame queue; sync holds the ticket).
+struct MaskPlan {
+    int G;                // parts per frame, 1 .. kMaskMaxSplit
+    bool tickets;         // work-groups take (frame, part) tickets from sync: G > 1 or the queue
+    int grid;             // work-groups: n_frames x G, at most slots (split) or queue
+    int queue;            // the frame queue in effect, else 0
+    size_t draws_bytes;   // 3 doubles per frame
+    size_t rec_bytes;     // mask_rec_bytes (GMM), else 0
+    size_t sync_bytes;    // with tickets, else 0
+    size_t parts_bytes;   // G > 1, else 0
+};
+MaskPlan mask_plan(int n_frames, int64_t total, int mode, int split, int slots, int queue);
+// The arguments of launch_mask_pose on storage type T (float: mask_pose.hip, double:
+// mask_pose_f64.hip).  order (nullable): the dispatch order of the frames (a device permutation).
+template <class T>
+struct MaskArgs {
+    const T* pts;
+    const T* flow;
+    const int64_t* frame_off;
+    int mode;
+    const uint8_t* mask_in;
+    const double* draws;
+    uint2* lloyd_rec;
+    int reflection;
+    uint8_t* bg_mask;
+    double* out;
+    uint32_t* sync;       // plan.sync_bytes
+    double* parts;        // plan.parts_bytes
+    const int32_t* order;
+};
+template <class T>
+hipError_t launch_mask_pose(hipStream_t s, int n_frames, const MaskPlan& plan, const MaskArgs<T>& a);
 int mask_pose_slots(int device);
 // ---- launcher (kabsch_f32.hip): the float32 slove_RT_by_SVD + Quaternion tail per frame; source
 // rows = dst + flow (f32) when flow is given, else src; keep_failures: leave frames whose status

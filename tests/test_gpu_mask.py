@@ -84,8 +84,8 @@ def test_full_size_batch_vs_oracle(oracle, dev):
 def test_frame_split_golden(dev, G):
     """ssf_set_mask_split: the GMM fit of one frame on G work-groups exchanging per-pass sums
     (G = 1: the B >= 256 bench path; the automatic choice is the resident work-group slots over
-    the launch's frames, at least 1 and at most the maximum split of 32 -- abi.hip,
-    mask_pose_batch -- so a 1-frame launch runs on 32 parts).  Labels,
+    the launch's frames, at least 1 and at most the maximum split of 32 -- mask_pose.hip,
+    mask_plan -- so a 1-frame launch runs on 32 parts).  Labels,
     k-means++ indices, iteration counts and the lower bound stay those of sklearn."""
     import ssf
     g = np.load(os.path.join(GOLDEN, "gmm_noseg_case2.npz"))
