@@ -136,7 +136,8 @@ SSF_DEV void assoc_finish(const float4* __restrict__ L, int64_t lo, const float*
 // every query exact (no 1-m band, no exhaustive phase).  Lower bounds: inside a searched strip,
 // dymin from the strip's actual y extent (fl(qy - yhi) <= fl(qy - py) by monotone rounding, so
 // fl(fl(dx^2) + fl(dymin^2)) <= the float distance); for the ring stop, the nominal strip edge
-// minus 1 mm (float strip assignment).  Candidates compare as (distance, original index).
+// minus strip_slack: 1 mm or, on extents of kilometres, 16 eps (|y0| + |y1| + |qy|) (float strip
+// assignment; derived in reg_strips.hpp).  Candidates compare as (distance, original index).
 // kSoa: the strip-major points as x | y | z float arrays and a u16 original index (configs[4]
 // frames); otherwise float4 with the index in .w.  A last frame above the launch's staging
 // capacity walks the x-sorted copy in global memory, unbounded (exact, slow, not expected).
@@ -217,6 +218,7 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
               [&](int, int r) { float4 pt = SP[r]; pt.w = __int_as_float(SI[r]); return pt; }, ml, T, SL, SX, SI16);
     const float y0 = geo.y0, W = geo.W;
     const int ns = geo.ns;
+    const float span = geo.span();
     auto strip_of = [&](float y) { return geo.strip_of(y); };
     const StripView<kSoa> v{SL, SX, SI16, ml};
 #ifdef SSF_STRIPS_STAMPS
@@ -286,6 +288,9 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
             for (float R = 2.0f;; R *= 2.0f) {
                 const bool unbounded = R > 4096.0f;
                 const float lim = unbounded ? __builtin_inff() : R * R;
+                // the whole W added here, not the 1 mm, carries the float error of the strip
+                // assignment at large extents (strip_of is monotone: a point within R of qs.y in
+                // y is in [sa, sb] already without either)
                 const int sa = unbounded ? 0 : strip_of(qs.y - R - W - 1e-3f);
                 const int sb = unbounded ? ns - 1 : strip_of(qs.y + R + W + 1e-3f);
                 for (int sidx = sa + gl; sidx <= sb; sidx += kCoopG) search(sidx, lim, qs, best, bc);
@@ -327,6 +332,7 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
         // hole, BASELINE configs[2]) therefore walks the points within ~2x its 1-NN distance,
         // not every point within the distance of the first point its own strip happens to hold.
         const int s0 = strip_of(qs.y);
+        const float slack = strip_slack(span, qs.y);                     // reg_strips.hpp
         for (float R = 2.0f;; R *= 2.0f) {
             const bool unbounded = R > 4096.0f;                          // uniform per lane
             const float lim = unbounded ? __builtin_inff() : R * R;
@@ -337,13 +343,13 @@ __global__ __launch_bounds__(kStripThreads) void k_associate_strips(
                 if (up) {
                     const int su = s0 + rr;
                     // every point of strips >= su has y >= y0 + su W (less float slack)
-                    const float gap = (y0 + (float)su * W) - qs.y - 1e-3f;
+                    const float gap = (y0 + (float)su * W) - qs.y - slack;
                     if (su >= ns || (gap > 0.0f && gap * gap > bnd)) up = false;
                     else search(su, lim, qs, best, bc);
                 }
                 if (dn) {
                     const int sd = s0 - rr;
-                    const float gap = qs.y - (y0 + (float)(sd + 1) * W) - 1e-3f;
+                    const float gap = qs.y - (y0 + (float)(sd + 1) * W) - slack;
                     if (sd < 0 || (gap > 0.0f && gap * gap > bnd)) dn = false;
                     else search(sd, lim, qs, best, bc);
                 }

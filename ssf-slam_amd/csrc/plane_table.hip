@@ -336,16 +336,17 @@ SSF_DEV void visit_1m(const StripView<false>& v, const StripLds& T, const StripG
 }
 
 // Every strip outward from q's, in rings of strips, while a strip can still hold a point with
-// d2 <= bound(): strip s0 +- r has |dy| >= (r - 1) W (less 1 mm of rounding slack).
+// d2 <= bound(): strip s0 +- r has |dy| >= (r - 1) W (less strip_slack, reg_strips.hpp).
 template <class Bound, class Body>
 SSF_DEV void visit_all(const StripView<false>& v, const StripLds& T, const StripGeo& g, int self, const float4& q,
                        Bound&& bound, Body&& body) {
     const float inf = __builtin_inff();
     const int s0 = g.strip_of(q.y);
     int p0 = self;
+    const float slack = strip_slack(g.span(), q.y);
     strip_visit(v, T, s0, p0, q, inf, bound, body);
     for (int r = 1; r < g.ns; ++r) {
-        const float lb = (float)(r - 1) * g.W - 0.001f;
+        const float lb = (float)(r - 1) * g.W - slack;
         if (lb > 0.0f && lb * lb > bound()) break;
         int pu = -1, pd = -1;
         if (s0 + r < g.ns) strip_visit(v, T, s0 + r, pu, q, inf, bound, body);
@@ -551,13 +552,14 @@ SSF_DEV void table_pick_walks(const float4* __restrict__ P, const StripView<fals
         pick_1m(P, v, T, g, j, q, s);
         const bool f1 = key_dist(s.d1) < 1.0f;
         const int prow = s.prow, s0 = g.strip_of(q.y), nstrip = 2 * g.ns;   // round order
+        const float slack = strip_slack(g.span(), q.y);
         auto strip_at = [&](int i) { return i == 0 ? s0 : ((i & 1) ? s0 + (i + 1) / 2 : s0 - i / 2); };
         auto ring_at = [&](int i) { return (i + 1) / 2; };
         // E: the smallest key of an other-ring point beyond 1 m
         double E = knn_key(__builtin_inff(), 0x7fffffff);
         for (int i0 = 0; i0 < nstrip; i0 += G) {
-            // a round's strips all have rings >= ring_at(i0): their |dy| >= (r - 1) W
-            const float lb = (float)(ring_at(i0) - 1) * g.W - 0.001f;
+            // a round's strips all have rings >= ring_at(i0): their |dy| >= (r - 1) W - slack
+            const float lb = (float)(ring_at(i0) - 1) * g.W - slack;
             if (i0 > 0 && lb > 0.0f && lb * lb > key_dist(E)) break;   // uniform per group
             const int i = i0 + gl, sidx = strip_at(i);
             if (i < nstrip && sidx >= 0 && sidx < g.ns) {
@@ -583,7 +585,7 @@ SSF_DEV void table_pick_walks(const float4* __restrict__ P, const StripView<fals
             const float lim = key_dist(E);
             int C = 0;
             for (int i0 = 0; i0 < nstrip; i0 += G) {
-                const float lb = (float)(ring_at(i0) - 1) * g.W - 0.001f;
+                const float lb = (float)(ring_at(i0) - 1) * g.W - slack;
                 if (C >= need || (i0 > 0 && lb > 0.0f && lb * lb > lim)) break;   // uniform per group
                 const int i = i0 + gl, sidx = strip_at(i);
                 int c = 0;

@@ -42,7 +42,23 @@ struct StripGeo {
     float y0, W, invW;
     int ns;
     SSF_DEV int strip_of(float y) const { return min(ns - 1, max(0, (int)((y - y0) * invW))); }
+    // |y0| + an upper bound of |y1| (|y1| <= |y0| + ns W): the frame's part of strip_slack
+    SSF_DEV float span() const { return 2.0f * fabsf(y0) + (float)ns * W; }
 };
+
+// Slack of a ring stop: what a search subtracts from a NOMINAL strip distance -- y0 + su W - qy
+// (the association's lane mode), (r - 1) W (the plane table's searches beyond 1 m) -- so that it
+// stays a lower bound of the float |dy| of every point of the strips it cuts off.  With
+// eps = 2^-24: strip_of puts p in a strip >= su when fl(fl(p.y - y0) invW) >= su, three roundings,
+// so p.y >= y0 + su W - 3 eps E, E = su W <= the extent (a query of the cloud itself is placed the
+// same way: 3 eps E more).  The stop forms fl(y0 + fl(su W)), eps E and eps Y more (Y = max |y|),
+// or fl((r - 1) W), eps E; then fl(. - qy) and fl(. - slack), eps (Y + |qy|) each; and the distance
+// it must not exceed is built on fl(qy - p.y), one more.  With S = |y0| + |y1| + |qy| >= E and
+// >= Y + |qy| that is at most 9 eps S; 16 eps S is taken.  Below S ~ 1 km the slack is the 1 mm
+// every scan has always had (no walk of a scan changes); at 30 km of extent it is ~7 cm.
+constexpr float kStripSlackMin = 1e-3f;
+constexpr float kStripSlackRel = 16.0f * 5.9604645e-8f;            // 16 eps
+SSF_DEV float strip_slack(float span, float qy) { return fmaxf(kStripSlackMin, kStripSlackRel * (span + fabsf(qy))); }
 
 // The plane table's strip image, kept for the association of the pairs whose LAST frame it is
 // (strips_build is deterministic and both kernels run it on the same x-sorted points with the

@@ -93,6 +93,9 @@ def associate(last, curr, q, t, valid=None):
     product) shortlist the three nearest, whose d2 are then recomputed as sum (x - L)^2; (d2, index)
     order.  The shortlist's error (2^-52 of |x|^2, 3e-9 m^2 at 5 km) cannot drop the winner of a
     pair whose gap the cases require to be >= 1e-3 relative, and a smaller gap shows in `gap`.
+    Exact, then, for gap >= 1e-3 and for ties among at most three points: a tie among four or more
+    (a lattice cell's centre) can leave the lowest index outside the shortlist of three --
+    associate_exact() has no shortlist and is the yardstick there.
     -> (nn [c] int, gap [c]: (second-best d2 - best d2) / second-best d2, keep [c] bool)."""
     L = np.asarray(last, np.float32)[:, :3].astype(np.float64)
     s = transform_to_last(np.asarray(curr)[:, :3], q, t).astype(np.float64)
@@ -113,6 +116,35 @@ def associate(last, curr, q, t, valid=None):
         nn[lo:lo + 1024] = cand[:, 0]
         if m > 1:
             gap[lo:lo + 1024] = np.where(d2[:, 1] > 0, (d2[:, 1] - d2[:, 0]) / np.where(d2[:, 1] > 0, d2[:, 1], 1.0), 0.0)
+    keep = np.ones(c, bool) if valid is None else np.asarray(valid)[nn] != 0
+    return nn, gap, keep
+
+
+def associate_exact(last, curr, q, t, valid=None):
+    """The 1-NN of :168 with nothing left out: the transformed query of transformToLast (:74-82,
+    float32) and the last points (float32), both converted exactly to float64; every one of the
+    c x m squared distances as sum (x - L)^2, never the expanded form; the winner the first of
+    np.lexsort((index, d2)), so an exact tie of any multiplicity goes to the lowest index.
+    Queries go in chunks of ~2e6 distances (m = 11 000 stays in memory).
+    -> (nn [c] int, gap [c]: (second-best d2 - best d2) / second-best d2, 0 on a tie, keep [c])."""
+    L = np.asarray(last, np.float32)[:, :3].astype(np.float64)
+    s = transform_to_last(np.asarray(curr)[:, :3], q, t).astype(np.float64)
+    c, m = len(s), len(L)
+    if m == 0:
+        return np.full(c, -1, np.int64), np.ones(c), np.zeros(c, bool)
+    nn = np.zeros(c, np.int64)
+    gap = np.ones(c)
+    step = max(1, 2_000_000 // m)
+    for lo in range(0, c, step):
+        x = s[lo:lo + step]
+        d2 = ((x[:, None, :] - L[None, :, :]) ** 2).sum(-1)
+        index = np.broadcast_to(np.arange(m), d2.shape)
+        order = np.lexsort((index, d2), axis=1)
+        nn[lo:lo + step] = order[:, 0]
+        if m > 1:
+            rows = np.arange(len(x))
+            first, second = d2[rows, order[:, 0]], d2[rows, order[:, 1]]
+            gap[lo:lo + step] = np.where(second > 0, (second - first) / np.where(second > 0, second, 1.0), 0.0)
     keep = np.ones(c, bool) if valid is None else np.asarray(valid)[nn] != 0
     return nn, gap, keep
 

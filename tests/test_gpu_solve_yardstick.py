@@ -47,7 +47,8 @@ def _views(pb, P, dev):
 
 def _launch(dev, cases, table_mode, bound=None):
     """One register() launch of `cases` (one solver, one max_iter).  table_mode: "brute" (no search
-    buffers), "sorted" (plane_table's buffers, normal / valid overwritten in place)."""
+    buffers), "sorted" (plane_table's buffers, normal / valid overwritten in place), "own_strips"
+    (sorted without the table's strip image: the association builds its strips itself)."""
     import ssf
     solver, iters = cases[0].solver, cases[0].max_iter
     assert all(c.solver == solver and c.max_iter == iters for c in cases)
@@ -67,7 +68,7 @@ def _launch(dev, cases, table_mode, bound=None):
     if table_mode == "brute":
         table = ssf.frontend.PlaneTable(torch.from_numpy(nrm).to(dev), torch.from_numpy(val).to(dev), None, None)
     else:
-        table = fe.plane_table(pb)
+        table = fe.plane_table(pb, strips=table_mode != "own_strips")
         table[0].copy_(torch.from_numpy(nrm).to(dev))
         table[1].copy_(torch.from_numpy(val).to(dev))
     pose = torch.tensor(np.stack([c.pose0 for c in cases]), dtype=torch.float64, device=dev)
@@ -88,6 +89,7 @@ def _launch(dev, cases, table_mode, bound=None):
     torch.cuda.synchronize()
     out = {k: v.cpu().numpy() for k, v in res.items() if v is not None}
     out["curr_off"] = h[:P + 1]
+    out["strip_image"] = getattr(table, "strips", None) is not None
     return out
 
 
