@@ -112,7 +112,8 @@ SSF_DEV void load_raw(const T* __restrict__ P, const T* __restrict__ Fl, int64_t
 
 // Cache policy of the point streams.  A frame's [flow, xyz] is 2.88 MB and
 // hundreds of frames are in flight, so no point byte read by a loop over a whole part is found
-// in a cache again: those loops (for_points_deep, for_point_pairs, the two k-means++ streams)
+// in a cache again: those loops (for_points_deep, for_point_pairs, the k-means++ distance stream
+// of a part above kKppBlocks blocks)
 // read with the non-temporal policy, global_load ... nt, and leave the L2 to the bytes that are
 // re-used -- the Lloyd records, the relabel queues and the gathers of relabelled points, which
 // stay at the default policy like every single-point read (each measured with nt and slower or
@@ -156,7 +157,11 @@ SSF_DEV double uni(double v) {
 // fn(i, x, val) runs for every slot of the last trip too (val = false past r1, x = the clamped
 // last point): a store under a branch in a streaming loop made the compiler drain the prefetches
 // at the join (the record-writing full pass took 411 k cycles against 264 k without records).
-template <int D, class Ts, class Fn>
+// kWaveTrips: a wave makes its trips together -- a lane whose own points have run out goes on
+// with val = false slots while any lane of its wave has one, so fn may use cross-lane operations
+// over whole 64-point blocks (wave w holds block (j >> 6) of the part at slot j).  The extra
+// slots add zeros: the sums keep their bits.
+template <int D, bool kWaveTrips = false, class Ts, class Fn>
 SSF_DEV void for_points_deep(const Ts* __restrict__ P, const Ts* __restrict__ Fl, int64_t r0, int64_t r1, Fn&& fn) {
     // frames of at most 2^32 / (3 sizeof(Ts)) points (mask_pose_batch rejects larger ones)
     if (r1 <= r0) return;                              // uniform (an empty part)
@@ -165,11 +170,12 @@ SSF_DEV void for_points_deep(const Ts* __restrict__ P, const Ts* __restrict__ Fl
     const uint32_t n = (uint32_t)(r1 - r0), T = blockDim.x, last = n - 1;
     constexpr uint32_t S = 3 * sizeof(Ts);
     const uint32_t j0 = threadIdx.x;
+    const uint32_t lead = kWaveTrips ? (j0 & 63u) : 0u;   // the lane's offset in its 64-point block
     auto load = [&](uint32_t k, Ts r[6]) { load3_off(Fb, k * S, r); load3_off(Pb, k * S, r + 3); };
     Ts buf[D][6];
 #pragma unroll
     for (int d = 0; d < D; ++d) load(min(j0 + d * T, last), buf[d]);
-    for (uint32_t base = j0; base < n; base += D * T) {
+    for (uint32_t base = j0; base - lead < n; base += D * T) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const uint32_t j = base + d * T;

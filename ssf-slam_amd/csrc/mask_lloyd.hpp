@@ -17,6 +17,57 @@ SSF_DEV uint32_t* lloyd_queue_base(uint2* rec, int64_t total, int n_frames, int6
     return reinterpret_cast<uint32_t*>(rec + lloyd_rec_count(total, n_frames)) + fb + kLloydSpareQueue * (int64_t)f;
 }
 
+// ---- the lane-0 algebra around one Lloyd labelling pass, shared by iteration 0 (labelled in
+//      the k-means++ candidate stream, mask_seed.hpp) and the loop of mask_lloyd.
+// Lane 0, before the fit's first labelling pass.
+SSF_DEV void lloyd_reset(MaskShared& S) {
+    S.strict = 0; S.done = 0; S.lfull = 1;
+    S.dg_cyc = S.dg_n = S.dg_lab = S.dg_wfull = S.dg_full1 = 0.0;
+}
+// Lane 0, before labelling pass `it`: the centres' squared norms S.csn and the pass's lhist row.
+SSF_DEV void lloyd_begin_pass(MaskShared& S, int it) {
+    double* h = S.lhist + 9 * it;
+    for (int k = 0; k < 2; ++k) {
+        double sn = 0.0;
+        for (int d = 0; d < 6; ++d) sn += S.cen[6 * k + d] * S.cen[6 * k + d];
+        S.csn[k] = sn;
+    }
+    for (int d = 0; d < 6; ++d) h[d] = S.cen[6 + d] - S.cen[d];
+    h[6] = S.csn[0] - S.csn[1];
+    h[7] = sqrt(S.csn[0]) + sqrt(S.csn[1]);
+    h[8] = S.csn[0] + S.csn[1];
+}
+// Lane 0, after labelling pass `it`: acc = the pass's 14 cluster sums (full) or sum deltas (skip
+// pass), changed / nlab = the frame's changed-label and relabelled counts, cost = the pass's
+// traffic in 24-byte-per-point units.  Writes lsum, km_iter, lfull, passes, cenp / csnp, the new
+// centres (an empty cluster keeps its centre), and strict / done from changed and the shift.
+SSF_DEV void lloyd_end_pass(MaskShared& S, int it, bool full, const double (&acc)[14], int changed, int nlab,
+                            int64_t n, double cost) {
+    S.passes += cost;
+    S.km_iter = it + 1;
+    for (int k = 0; k < 14; ++k) S.lsum[k] = full ? acc[k] : S.lsum[k] + acc[k];
+    // the first passes move the centres most (typically 35-45 % of the points would be
+    // relabelled): full passes through it = 3, then skip passes while they relabel < 1/4
+    S.lfull = full ? it < kLloydFullPasses - 1 : nlab * kLloydRefull > n;
+    for (int k = 0; k < 12; ++k) S.cenp[k] = S.cen[k];
+    S.csnp[0] = S.csn[0]; S.csnp[1] = S.csn[1];
+    double shift = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        const double wgt = S.lsum[7 * k];
+        double sh = 0.0;
+        for (int d = 0; d < 6; ++d) {
+            const double nc = wgt > 0.0 ? S.lsum[7 * k + 1 + d] * (1.0 / wgt) : S.cen[6 * k + d];
+            const double df = nc - S.cen[6 * k + d];
+            sh += df * df;
+            S.cen[6 * k + d] = nc;
+        }
+        sh = sqrt(sh);
+        shift += sh * sh;
+    }
+    if (changed == 0) { S.strict = 1; S.done = 1; }
+    else if (shift <= S.tol) S.done = 1;
+}
+
 // ---- Lloyd iterations (_kmeans_single_lloyd, max_iter 300) with exact label skipping.
 //      A point's label at pass t is the sign of g_t = D0 - D1 (D_k = -2 v.c_k + |c_k|^2, the
 //      expression the label is computed with).  In exact arithmetic g_t(v) = 2 v.w_t + s_t
@@ -29,8 +80,11 @@ SSF_DEV uint32_t* lloyd_queue_base(uint2* rec, int64_t total, int n_frames, int6
 //      differ.  Skipped points keep their label, so the labels, the changed-label count and
 //      the strict-convergence decision are those of the full pass; the cluster sums are
 //      updated by the points that changed label.
-// Reads the k-means++ centres S.cen (cenp, csnp zero) and S.tol; leaves the final centres in
-// S.cen, the last labelling pass's in S.cenp / csnp, and S.strict, km_iter, passes.
+//      Iteration 0 (every point, against the k-means++ centres, no records) is not run here:
+//      mask_kmeanspp labels it in its candidate stream and ends it with lloyd_end_pass.
+// Reads iteration 0's result (S.cen, cenp / csnp, lsum, lfull, done, km_iter = 1) and S.tol;
+// leaves the final centres in S.cen, the last labelling pass's in S.cenp / csnp, and S.strict,
+// km_iter, passes.
 // lloyd_rec: the launch's record / queue buffer; total: the points of all n_frames frames.
 template <class T>
 SSF_DEV bool mask_lloyd(MaskCtx<T>& C, const MaskLds& L, uint2* __restrict__ lloyd_rec, int64_t total,
@@ -41,22 +95,12 @@ SSF_DEV bool mask_lloyd(MaskCtx<T>& C, const MaskLds& L, uint2* __restrict__ llo
     const T* Fl = C.Fl;
     const double (&mean)[6] = C.mean;
     const int64_t n = C.n, r0 = C.X.r0, r1 = C.X.r1;
-    if (tid == 0) { S.strict = 0; S.done = 0; S.lfull = 1; S.dg_cyc = S.dg_n = S.dg_lab = S.dg_wfull = S.dg_full1 = 0.0; }
+    static_assert(kLloydFullPasses >= 2, "iteration 0 (mask_kmeanspp) writes no records");
+    if (S.done) return true;                  // uniform: iteration 0 met tol (or no label changed)
     uint2* __restrict__ LR = lloyd_rec_base(lloyd_rec, C.fb, C.f);
     uint32_t* __restrict__ LQ = lloyd_queue_base(lloyd_rec, total, n_frames, C.fb, C.f);
-    for (int it = 0; it < kLloydMax; ++it) {
-        if (tid == 0) {
-            double* h = S.lhist + 9 * it;
-            for (int k = 0; k < 2; ++k) {
-                double sn = 0.0;
-                for (int d = 0; d < 6; ++d) sn += S.cen[6 * k + d] * S.cen[6 * k + d];
-                S.csn[k] = sn;
-            }
-            for (int d = 0; d < 6; ++d) h[d] = S.cen[6 + d] - S.cen[d];
-            h[6] = S.csn[0] - S.csn[1];
-            h[7] = sqrt(S.csn[0]) + sqrt(S.csn[1]);
-            h[8] = S.csn[0] + S.csn[1];
-        }
+    for (int it = 1; it < kLloydMax; ++it) {
+        if (tid == 0) lloyd_begin_pass(S, it);
         __syncthreads();
         if (tid < it) {   // drift bounds of this pass against every earlier labelling pass
             const double* h = S.lhist + 9 * it;
@@ -214,13 +258,9 @@ SSF_DEV bool mask_lloyd(MaskCtx<T>& C, const MaskLds& L, uint2* __restrict__ llo
             // of records written when wrec); a skip pass reads 8 B of records per point and
             // 24 B per relabelled point, and writes (reads) 8 B of record + 4 (4) B of queue
             // per relabel
-            S.passes += full ? 1.0 + (wrec ? 8.0 / 24.0 : 0.0)
-                             : (8.0 * (double)n + 40.0 * (double)nlab) / (24.0 * (double)n);
-            S.km_iter = it + 1;
-            for (int k = 0; k < 14; ++k) S.lsum[k] = full ? acc[k] : S.lsum[k] + acc[k];
-            // the first passes move the centres most (typically 35-45 % of the points would be
-            // relabelled): full passes through it = 3, then skip passes while they relabel < 1/4
-            S.lfull = full ? it < kLloydFullPasses - 1 : nlab * kLloydRefull > n;
+            lloyd_end_pass(S, it, full, acc, changed, nlab, n,
+                           full ? 1.0 + (wrec ? 8.0 / 24.0 : 0.0)
+                                : (8.0 * (double)n + 40.0 * (double)nlab) / (24.0 * (double)n));
 #ifdef SSF_MASK_STAMPS
             // diagnostic: cycles and relabelled points of the skip passes (k_mask_pose stamps
             // build only; reported through the k-means++ centre slots, which it overwrites)
@@ -228,23 +268,6 @@ SSF_DEV bool mask_lloyd(MaskCtx<T>& C, const MaskLds& L, uint2* __restrict__ llo
             else if (it == kLloydFullPasses - 1) S.dg_wfull = (double)(__builtin_amdgcn_s_memtime() - pass_t0);
             else if (it == 1) S.dg_full1 = (double)(__builtin_amdgcn_s_memtime() - pass_t0);
 #endif
-            for (int k = 0; k < 12; ++k) S.cenp[k] = S.cen[k];
-            S.csnp[0] = S.csn[0]; S.csnp[1] = S.csn[1];
-            double shift = 0.0;
-            for (int k = 0; k < 2; ++k) {
-                const double wgt = S.lsum[7 * k];
-                double sh = 0.0;
-                for (int d = 0; d < 6; ++d) {
-                    const double nc = wgt > 0.0 ? S.lsum[7 * k + 1 + d] * (1.0 / wgt) : S.cen[6 * k + d];
-                    const double df = nc - S.cen[6 * k + d];
-                    sh += df * df;
-                    S.cen[6 * k + d] = nc;
-                }
-                sh = sqrt(sh);
-                shift += sh * sh;
-            }
-            if (changed == 0) { S.strict = 1; S.done = 1; }
-            else if (shift <= S.tol) S.done = 1;
         }
         __syncthreads();
         if (S.done) break;

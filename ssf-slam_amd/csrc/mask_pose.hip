@@ -3,10 +3,16 @@
 //
 // One work-group owns one frame and runs the WHOLE GaussianMixture(n_components=2).fit_predict
 // on device (sklearn 1.7.2 semantics, f64 arithmetic on the f32 point / flow storage):
-//   pass 0      X = [flow, xyz]: column means and variances (KMeans centering, tol)
-//   k-means++   distances to the first centre (index chosen from the caller's RandomState
-//               draw), in-order chunked prefix scan -> the two local-trial candidates, potentials
-//   Lloyd       one streaming pass per iteration (labels, per-cluster sums, changed-label count)
+//   pass 0      X = [flow, xyz]: column means and variances (KMeans centering, tol); the same
+//               stream forms the distances to the first k-means++ centre (index chosen from the
+//               caller's RandomState draw, so known before any point is read) and leaves their
+//               totals per 64-point block
+//   k-means++   in-order prefix scan over the block totals -> the two local-trial candidates;
+//               one stream for their potentials, which also labels Lloyd iteration 0 against
+//               (first centre, candidate) for both candidates: the winner's cluster sums are
+//               that iteration's
+//   Lloyd       from iteration 1: one streaming pass per iteration (labels, per-cluster sums,
+//               changed-label count)
 //   GMM init    one-hot responsibilities -> shifted first/second moments -> 6x6 Cholesky
 //   EM          ONE fused pass per iteration: E-step (log-prob difference of the two components,
 //               responsibilities) and the M-step moment sums of the next parameters together
@@ -24,8 +30,9 @@
 // MaskShared (each stage's comment says what it reads and writes there):
 //   mask_common.hpp    constants, MaskShared, the point loads and the streaming loops
 //   mask_exchange.hpp  Split, the exchange between a frame's parts, MaskCtx, MaskLds
-//   mask_seed.hpp      mask_pass0, mask_kmeanspp
-//   mask_lloyd.hpp     mask_lloyd and the layout of its record / queue buffer
+//   mask_seed.hpp      mask_pass0, mask_kmeanspp (ends in Lloyd iteration 0)
+//   mask_lloyd.hpp     mask_lloyd, the lane-0 algebra around a labelling pass, and the layout of
+//                      the record / queue buffer
 //   mask_em.hpp        mask_gmm_init, mask_em
 //   mask_final.hpp     mask_final, mask_flip, mask_given
 //   mask_gmm.hpp       gmm_params2 and the per-point E-step pieces

@@ -47,8 +47,8 @@ def main():
           f"{o[:, 1].mean():.3e}, M-step {o[:, 2].mean():.3e} cycles")
     for k, nme in enumerate(names):
         per = ""
-        if nme == "lloyd":
-            per = f"  per pass {d[:, k].mean() / o[:, 19].mean():.3e}"
+        if nme == "lloyd":      # iteration 0 is labelled in the k-means++ phase's candidate stream
+            per = f"  per pass {d[:, k].mean() / max(o[:, 19].mean() - 1.0, 1.0):.3e}"
         if nme == "em":
             per = f"  per pass {d[:, k].mean() / o[:, 20].mean():.3e}"
         print(f"  {nme:12s} {d[:, k].mean():.3e} cyc  {100 * d[:, k].mean() / tot:5.1f} %{per}")
